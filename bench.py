@@ -10,7 +10,14 @@ Workload (BASELINE.json configs[2], the metric's configuration):
   whole chain; with N GPUs the 64 shards are split N ways (strong scaling, RCCL
   all-gathers over xGMI for the cross-shard exchanges).
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+A plain run sets up, warms up, times the K steps and prints the result line (metric, value,
+unit, ms_per_step, ...).  --full adds everything else the benchmark measures, each in a run of
+its own outside the timed region: the per-kernel HIP-event pass and the roofline figures, the
+ingest timings, the chain trace diagnostics, the covariance error against the synthetic truth
+(this chain and a separate converged one) and the CPU baselines.  --dump-outputs DIR writes
+what the timed path computed in its last step (dump_outputs).
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
        (N > 1: python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...)
 """
 from __future__ import annotations
@@ -186,6 +193,36 @@ def cpu_faithful_run(n, p, g, K, rho):
                       f"divideconquer.m:97-177 (restatement, not MATLAB), {dt:.1f} s"}
 
 
+DUMP_STATE_BYTES = 56_000_000      # state arrays: whole below this total, else each capped at 1/8 of it
+DUMP_SIGMA_BYTES = 6_000_000       # Sigmaout: whole columns within this, at most 32 of them
+DUMP_SEED = 20161209
+
+
+def dump_outputs(smp, out_dir, suffix=""):
+    """What a caller of the timed path receives after its last step, as out_dir/<name><suffix>.npy
+    (float64, under 64 MB in all): every field of get_state() as <field>.npy, and Sigma_cols.npy,
+    columns of Sigmaout (p x c: stripes of 8 adjacent columns a fixed seed picks, ascending; 32
+    columns while p allows, DUMP_SIGMA_BYTES at most).  If the state exceeds
+    DUMP_STATE_BYTES, each field larger than an eighth of that is cut to a fixed seeded sample of
+    its elements (column-major order, ascending).  Same arguments, same build: same files."""
+    out_dir.mkdir(parents=True, exist_ok=True)
+    r = np.random.Generator(np.random.PCG64(DUMP_SEED))
+    state = smp.get_state()
+    whole = sum(a.nbytes for a in state.values()) <= DUMP_STATE_BYTES
+    cap = DUMP_STATE_BYTES // 8 // 8
+    for f, a in state.items():
+        if not whole and a.size > cap:
+            a = a.reshape(-1, order="F")[np.sort(r.choice(a.size, size=cap, replace=False))]
+        np.save(out_dir / f"{f}{suffix}.npy", np.ascontiguousarray(a, dtype=np.float64))
+    p = smp.P * smp.g
+    ncols = int(min(32, p, max(1, DUMP_SIGMA_BYTES // (8 * p))))
+    width = min(8, ncols)                                       # stripes of `width` adjacent columns
+    starts = np.sort(r.choice(p // width, size=ncols // width, replace=False)) * width
+    parts = [smp.get_sigma_cols(int(c), width) for c in starts]     # collective when the shards are split
+    if parts[0] is not None:
+        np.save(out_dir / f"Sigma_cols{suffix}.npy", np.ascontiguousarray(np.hstack(parts), dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -197,6 +234,13 @@ def main():
     ap.add_argument("--P", type=int, default=312)
     ap.add_argument("--n", "--nobs", dest="n", type=int, default=1000)   # --nobs under torchrun (--n is ambiguous there)
     ap.add_argument("--K", type=int, default=30)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need, outside the timed region: per-kernel "
+                         "HIP-event pass + roofline, ingest timings, trace diagnostics, covariance error (this "
+                         "chain and a converged one), CPU baselines; the options below this one shape those legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the state and a seeded sample of Sigmaout columns as "
+                         "DIR/<name>.npy (float64, under 64 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-steps", type=int, default=10)
     ap.add_argument("--no-faithful", action="store_true", help="skip the faithful-loop CPU leg (~30 s)")
@@ -250,7 +294,8 @@ def main():
 
     g, P, n, K, rho, thin = args.g, args.P, args.n, args.K, 0.5, args.thin
     p = g * P
-    n_prof = 0 if args.no_profile else args.steps     # untimed per-kernel profiling pass
+    full = args.full
+    n_prof = args.steps if full and not args.no_profile else 0     # untimed per-kernel profiling pass (--full)
     N = args.warmup + n_prof + args.steps
     burnin, mcmc = 0, N
     Y, L0, sig2 = synth_data(n, p, factors=True)
@@ -259,7 +304,8 @@ def main():
     device = local_rank % ndev
     # driver half on the device: dc:31-38 column scan, then dc:48-59
     # gather + standardise by dcfm_set_data_raw below; Y crosses PCIe once per call
-    dcfm.count_nonzero_columns(Y[:, :64], device=device)      # first launch loads the code object
+    if full:
+        dcfm.count_nonzero_columns(Y[:, :64], device=device)      # first launch loads the code object
     nnz, ms_nnz = dcfm.count_nonzero_columns(Y, device=device, return_ms=True)
     keep = np.flatnonzero(nnz != 0)
     pk = keep.size
@@ -280,7 +326,8 @@ def main():
         dist.broadcast_object_list(obj, src=0)
         smp.comm_init(obj[0])
     cols = dcfm.shard_columns(keep, init.varind, P, s0, gl)
-    smp.set_data_raw(Y, cols)                 # first launches load the code objects
+    if full:
+        smp.set_data_raw(Y, cols)             # first launches load the code objects
     t_ing = time.perf_counter()
     _, ms_std = smp.set_data_raw(Y, cols)
     t_ing = time.perf_counter() - t_ing
@@ -294,7 +341,8 @@ def main():
     t_init = time.perf_counter()
     smp.init_state()                          # dcfm_init_state: Philox, iteration-0 counters
     ingest["init_state_ms"] = round((time.perf_counter() - t_init) * 1e3, 2)
-    U_true, s_true = dcfm.truth_factors(L0, sig2, Y, keep, init.varind)
+    if full:
+        U_true, s_true = dcfm.truth_factors(L0, sig2, Y, keep, init.varind)
     del Y
 
     have_torch_gpu = torch.cuda.is_available()
@@ -307,8 +355,8 @@ def main():
         if world > 1:
             dist.barrier()
 
-    # chain trace over the untimed warmup + profiling iterations only
-    n_trace = args.warmup + n_prof
+    # chain trace over the untimed warmup + profiling iterations only (--full)
+    n_trace = args.warmup + n_prof if full else 0
     if n_trace >= 4:
         smp.set_trace(n_trace)
     smp.run(1, args.warmup)
@@ -331,7 +379,8 @@ def main():
         trace = smp.get_trace()
         smp.set_trace(0)                    # the timed region records nothing
     # (2) the timed region: events only around the roofline kernel (live duration); on every
-    #     --timed-samples N launches (default 4 of the region's, evenly spaced; 0: every launch)
+    #     --timed-samples N launches (default 4 of the region's, evenly spaced; 0: every launch).
+    #     A plain run has no per-kernel table, hence no roofline kernel and no events at all.
     prof_stride = 1 if dominant == "k_assemble" or args.timed_samples <= 0 else max(1, args.steps // args.timed_samples)
     if dominant:
         smp.set_profiling_kernels([dominant], stride=prof_stride)
@@ -343,11 +392,13 @@ def main():
     live = smp.kernel_stats().get(dominant) if dominant else None
     saved_prof = sum(1 for t in range(args.warmup + 1, args.warmup + 1 + n_prof) if t % thin == 0)
     saved_in_region = sum(1 for t in range(first_t, first_t + args.steps) if t % thin == 0)
+    if args.dump_outputs:
+        dump_outputs(smp, Path(args.dump_outputs), f".rank{rank}" if world > 1 else "")
     # (3) after the timed region: the posterior-mean covariance error against the synthetic
     #     truth on the device (dcfm_sigma_error) — one norms-only pass (its HBM rate: the full
     #     p x p read from the stored triangle, 8 p^2 bytes) and a Lanczos operator norm
     sig_err = None
-    if args.err_iters > 0:
+    if full and args.err_iters > 0:
         sync()
         te = time.perf_counter()
         e0 = smp.sigma_error(U_true, s_true, iters=0)
@@ -366,7 +417,7 @@ def main():
     #     MCMC 5,000, thin 5) from its own init, outside the timed region; its posterior-mean
     #     Sigmaout against the synthetic truth, with split-R-hat / ESS of the MCMC part's trace
     converged = None
-    if world == 1 and args.converged_mcmc > 0 and args.err_iters > 0:
+    if full and world == 1 and args.converged_mcmc > 0 and args.err_iters > 0:
         cb, cm = args.converged_burnin, args.converged_mcmc
         smc = dcfm.Sampler(n, P, g, K, rho, cb, cm, thin, seed=7, device=device, asm_batch=args.asm_batch)
         try:
@@ -480,21 +531,25 @@ def main():
                                f"{', exact residual (k_resid)' if args.exact_residual else ''}",
                    "global_batch": n,
                    "parallelism": f"chains{world} (1 per GPU)" if chains else f"shards{g}/gpus{world}"},
-        "roofline": roof,
+        "full": full,
         "build": bid,
         "config_key": ckey,
     }
+    if full:
+        out["roofline"] = roof
     if "k_assemble" in kern:
         out["assembly_mfma_util"] = round(kern["k_assemble"]["tflops"] / FP64_MFMA_PEAK_TFLOPS, 4)
-    out["kernels"] = kern
+    if full:
+        out["kernels"] = kern
     if sig_err:
         out["sigma_error"] = sig_err
     if converged:
         out["sigma_error_converged"] = converged
-    out["ingest"] = ingest
+    if full:
+        out["ingest"] = ingest
     if diag:
         out["diagnostics"] = diag
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_run(n, p, g, K, rho, steps=args.cpu_steps, thin=thin)
         if not args.no_faithful:
             out["cpu_baseline_faithful"] = cpu_faithful_run(n, p, g, K, rho)

@@ -94,7 +94,7 @@ def test_bench_chains_two_ranks(tmp_path):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), str(ROOT / "bench.py"),
-           "--gpus", "2", "--chains", "--steps", "10", "--warmup", "4", "--g", "8", "--P", "50",
+           "--gpus", "2", "--chains", "--full", "--steps", "10", "--warmup", "4", "--g", "8", "--P", "50",
            "--nobs", "200", "--K", "10", "--no-cpu-baseline", "--err-iters", "0", "--asm-batch", "4"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -9,7 +9,7 @@ PKG=a-divide-and-conquer-strategy-for-high-dimensional-bayesian-factor-models_am
 mkdir -p gpurun_out; export TMPDIR=/tmp
 cp $PKG/libdcfm.so /tmp/libdcfm_intree.so
 trap 'cp /tmp/libdcfm_intree.so "$ROOT/$PKG/libdcfm.so"' EXIT   # the product build comes back on any exit
-BENCH="bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --converged-mcmc 0 $BENCH_EXTRA"
+BENCH="bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline --converged-mcmc 0 $BENCH_EXTRA"
 for r in $(seq 1 $R); do
   for V in "$@"; do
     cp build/ab/libdcfm_$V.so $PKG/libdcfm.so

@@ -13,9 +13,9 @@ if [ "$PHASE" = "c3" ]; then
   timeout -k 10 180 python -u -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke_$TAG.log 2>&1 || { echo "smoke failed"; tail gpurun_out/smoke_$TAG.log; exit 1; }
   tail -1 gpurun_out/smoke_$TAG.log
 fi
-C3="--gpus 1 --steps 20 --warmup 5"
-C4="--g 8 --P 1250 --n 2000 --K 100 --steps 100 --warmup 10"
-C5="--g 256 --P 391 --n 2000 --K 30 --steps 30 --warmup 5"
+C3="--gpus 1 --steps 20 --warmup 5 --full"
+C4="--g 8 --P 1250 --n 2000 --K 100 --steps 100 --warmup 10 --full"
+C5="--g 256 --P 391 --n 2000 --K 30 --steps 30 --warmup 5 --full"
 run() {   # name, bench args, extra bench args (not part of the profiled command)
   local N=$1 A=$2 X=$3
   bash tools/profile_round.sh $N $A || exit 1

@@ -11,7 +11,8 @@ ARGS="$@"
 [ -z "$ARGS" ] && ARGS="--gpus 1 --steps 20 --warmup 5"
 export TMPDIR=/tmp
 OUT=$GRAFT_REPO_ROOT/gpurun_out
-BENCH="python3 $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --converged-mcmc 0 $ARGS"   # no converged leg: the summary takes the timed region as the last dispatches
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
+BENCH="python3 $ROOT/bench.py --full --no-cpu-baseline --converged-mcmc 0 $ARGS"   # --full: the per-kernel pass before the timed region, as the bench line the summary is matched to; no converged leg: the summary takes the timed region as the last dispatches
 cd /tmp
 timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_${TAG} -o run -- $BENCH > $OUT/prof_${TAG}.log 2>&1 || { echo "trace failed"; exit 1; }
 timeout -s KILL 200 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/prof_${TAG}_fetch -o run -- $BENCH > $OUT/prof_${TAG}_fetch.log 2>&1 || { echo "fetch pass failed"; exit 1; }

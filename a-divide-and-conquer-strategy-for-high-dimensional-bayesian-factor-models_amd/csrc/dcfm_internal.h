@@ -37,6 +37,8 @@ namespace dcfm {
 
 constexpr int KP = 32;         // padded factor width of the narrow (K <= 32) kernels
 constexpr int KP_MAX = 128;    // widest supported padding (K <= 128, config c4 has K = 100)
+// padded factor width KW (Dims::kp) of K factors: the kernels are instantiated for these three
+constexpr int padded_width(int K) { return K <= 32 ? 32 : (K <= 64 ? 64 : 128); }
 constexpr int ASM_TILE = 128;  // covariance-assembly output tile
 // Wide paths (KW >= 64) keep E_m = eta_m' eta_m in the loading-row kernel's layout: the
 // upper 16x16 tiles (Kc <= I) of the KW/16 x KW/16 tile grid, tile t = etile(KW/16, Kc, I) in
@@ -115,7 +117,7 @@ struct Bufs {
                                        // [2 + chunk] = k_wcol A_m of the chunk out,
                                        // [SYNC_ZM + m] = k_wcol Z operators of shard m out
     double *msg_all;                   // packed gather target (fused, nranks > 1), else null
-    double *agree;                     // 3 doubles: the failure counts of a collective call (dcfm.hip agree)
+    double *agree;                     // 3 doubles: the failure counts of a collective call (comm.hip agree)
     int *rflag;                        // K > 32: [G][PP / 32] 32-row tiles whose SS identity the guard of
                                        // k_lambda_w rejected (k_resid_flagged redoes them and clears the flag)
     int2 *tiles;

@@ -435,9 +435,7 @@ __device__ __forceinline__ void z_eps(const Dims &d, const DrawsDev &dr, int64_t
         for (int t = 0; t < 4; ++t) {
             const int kk = 8 * t + 2 * q;
             double n0 = 0.0, n1 = 0.0;
-#ifndef DCFM_DEV_NO_ZNORM   // timing-only dev build: zero normals
             if (live && kk < d.K) rng.normal2(SITE_Z, (uint32_t)mg, (uint32_t)i, (uint32_t)(4 * t + q), (uint32_t)iter, n0, n1);
-#endif
             ev[t].x = n0;
             ev[t].y = (kk + 1 < d.K) ? n1 : 0.0;
         }
@@ -887,16 +885,16 @@ __global__ __launch_bounds__(1024) void k_xdraw(Dims d, const double *__restrict
 // IS_E: the A operand is eta itself, columns te*32.. (Yp = nullptr; Xa/Za point at
 // them); SAME_T: te == kt, so the A operand is the B operand (no extra loads).
 // PS: the block computes only the k columns of parity par (acc[.][0]); same per-element order
-// ETA (wide): Xp / Xa point at eta itself (formed once per iteration by k_eta into the free W buffer,
-// with the same eta_of), Zp / Za unused: one load per operand instead of two
-template <int KW, bool IS_E, bool SAME_T, bool PS = false, bool ETA = false>
+// ETA (wide, KW > KP): Xp / Xa point at eta itself (formed once per iteration by k_eta into the free W
+// buffer, with the same eta_of), Zp / Za unused: one load per operand instead of two
+template <int KW, bool IS_E, bool SAME_T, bool PS = false>
 __device__ __forceinline__ void cpass_wave(const Dims &d, const double *__restrict__ Yp,
                                            const double *__restrict__ Xp,
                                            const double *__restrict__ Zp,
                                            const double *__restrict__ Xa,
                                            const double *__restrict__ Za, int s0, int nsw,
                                            int q, d4 (&acc)[2][2], int par = 0) {
-    constexpr bool EXTRA = IS_E && !SAME_T;
+    constexpr bool EXTRA = IS_E && !SAME_T, ETA = KW > KP;
     d2 yA[4], xA[4], zA[4], yB[4], xB[4], zB[4];
     auto load = [&](int s, d2 (&y)[4], d2 (&x)[4], d2 (&z)[4]) {
 #pragma unroll
@@ -910,7 +908,7 @@ __device__ __forceinline__ void cpass_wave(const Dims &d, const double *__restri
                 const d2 xa = *reinterpret_cast<const d2 *>(Xa + (size_t)i * KW);
                 if (ETA) {
                     y[u] = xa;
-                } else {
+                } else {   // compiled for KW == KP only, where te == kt always (one eta column tile)
                     const d2 za = *reinterpret_cast<const d2 *>(Za + (size_t)i * KW);
                     y[u].x = eta_of(d.sr, d.s1r, xa.x, za.x);
                     y[u].y = eta_of(d.sr, d.s1r, xa.y, za.y);
@@ -946,10 +944,7 @@ __device__ __forceinline__ void cpass_wave(const Dims &d, const double *__restri
     }
 }
 
-template <int KW> constexpr int cp_waves() { return 4; }
-#ifndef DCFM_WIDE_ETA
-#define DCFM_WIDE_ETA 1
-#endif
+constexpr int CP_WAVES = 4;
 // PS (K <= 32, where the launch would leave CUs idle): each block computes one parity of its
 // 32 k columns (twice the blocks, the pair adjacent: Y from L2); per-element order unchanged
 // ndel > 0 (fused K <= 32 chain): the last ndel blocks run the previous iteration's delta / tau
@@ -960,17 +955,16 @@ template <int KW> constexpr int cp_waves() { return 4; }
 // SIMD); measured neutral at c3 and c4 (42.4 vs 42.9 us, 132 vs 135 us), kept for the
 // occupancy headroom
 template <int KW, bool PS = false>
-__global__ __launch_bounds__(64 * cp_waves<KW>()) __attribute__((amdgpu_waves_per_eu(3))) void k_cpass(Dims d, const double *__restrict__ Y,
+__global__ __launch_bounds__(64 * CP_WAVES) __attribute__((amdgpu_waves_per_eu(3))) void k_cpass(Dims d, const double *__restrict__ Y,
                                                               const double *__restrict__ X,
                                                               const double *__restrict__ Z,
                                                               double *__restrict__ C, double *__restrict__ E,
                                                               DrawsDev dr, const double *__restrict__ sall,
                                                               DeltaArgs da, int ndel) {
-    constexpr int NWV = cp_waves<KW>();
-    __shared__ double red[NWV][32][33];
+    __shared__ double red[CP_WAVES][32][33];
     const int nbc = gridDim.x - ndel;
     if ((int)blockIdx.x >= nbc) {
-        const int m = (blockIdx.x - nbc) * NWV + (threadIdx.x >> 6);
+        const int m = (blockIdx.x - nbc) * CP_WAVES + (threadIdx.x >> 6);
         if (m < d.g)
             delta_shard(d, sall, da.delta_in, da.tau_in, da.delta_out, da.tau_out, dr, da.iter, m, threadIdx.x & 63);
         return;
@@ -989,21 +983,21 @@ __global__ __launch_bounds__(64 * cp_waves<KW>()) __attribute__((amdgpu_waves_pe
     const int r = lane & 15, q = lane >> 4;
     const double *Yp = Y + (size_t)m * d.NP * d.PP + c0 + 2 * r;
     // wide: X is eta [G][NP][KW] (k_eta, launch_cpass), so the shard's rows
-    constexpr bool ETA = KW > KP && DCFM_WIDE_ETA;
+    constexpr bool ETA = KW > KP;
     const double *Xs = ETA ? X + (size_t)m * d.NP * KW : X;
     const double *Xp = Xs + 32 * kt + 2 * r;
     const double *Zp = Z + (size_t)m * d.NP * KW + 32 * kt + 2 * r;
     const double *Xa = Xs + 32 * te + 2 * r;
     const double *Za = Z + (size_t)m * d.NP * KW + 32 * te + 2 * r;
-    const int nsw = d.NP / (4 * NWV);          // k-steps (4 rows each) per wave
+    const int nsw = d.NP / (4 * CP_WAVES);          // k-steps (4 rows each) per wave
     d4 acc[2][2];
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
         for (int b = 0; b < 2; ++b) acc[a][b] = d4{0.0, 0.0, 0.0, 0.0};
-    if (!isE) cpass_wave<KW, false, false, PS, ETA>(d, Yp, Xp, Zp, Xa, Za, wave * nsw, nsw, q, acc, par);
-    else if (te == kt) cpass_wave<KW, true, true, PS, ETA>(d, Yp, Xp, Zp, Xa, Za, wave * nsw, nsw, q, acc, par);
-    else cpass_wave<KW, true, false, PS, ETA>(d, Yp, Xp, Zp, Xa, Za, wave * nsw, nsw, q, acc, par);
+    if (!isE) cpass_wave<KW, false, false, PS>(d, Yp, Xp, Zp, Xa, Za, wave * nsw, nsw, q, acc, par);
+    else if (te == kt) cpass_wave<KW, true, true, PS>(d, Yp, Xp, Zp, Xa, Za, wave * nsw, nsw, q, acc, par);
+    else cpass_wave<KW, true, false, PS>(d, Yp, Xp, Zp, Xa, Za, wave * nsw, nsw, q, acc, par);
     // D row rho = q + 4g -> column c0 + 2 rho + ta;  D col r -> k = 2r + tb
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
@@ -1019,16 +1013,11 @@ __global__ __launch_bounds__(64 * cp_waves<KW>()) __attribute__((amdgpu_waves_pe
         }
     }
     __syncthreads();
-    auto tsum = [&](int a, int b) {
-        if constexpr (NWV == 8)
-            return ((red[0][a][b] + red[1][a][b]) + (red[2][a][b] + red[3][a][b])) +
-                   ((red[4][a][b] + red[5][a][b]) + (red[6][a][b] + red[7][a][b]));
-        else
-            return (red[0][a][b] + red[1][a][b]) + (red[2][a][b] + red[3][a][b]);
-    };
+    static_assert(CP_WAVES == 4, "tsum is the canonical tree over four waves");
+    auto tsum = [&](int a, int b) { return (red[0][a][b] + red[1][a][b]) + (red[2][a][b] + red[3][a][b]); };
     if (KW > KP && isE) {   // wide: E_m in the loading-row kernel's tile layout (etile_index), upper tiles
         double *Em = E + (size_t)m * KW * KW;
-        for (int e = threadIdx.x; e < 32 * 32; e += 64 * NWV) {
+        for (int e = threadIdx.x; e < 32 * 32; e += 64 * CP_WAVES) {
             const int a = e >> 5, b = e & 31, R = 32 * te + a, Cc = 32 * kt + b;
             if ((R >> 4) <= (Cc >> 4)) Em[etile_index(KW / 16, R, Cc)] = tsum(a, b);
         }
@@ -1037,13 +1026,13 @@ __global__ __launch_bounds__(64 * cp_waves<KW>()) __attribute__((amdgpu_waves_pe
     double *out = isE ? (E + (size_t)m * KW * KW + (size_t)(32 * te) * KW + 32 * kt)
                       : (C + ((size_t)m * d.PP + c0) * KW + 32 * kt);
     if (PS) {   // this block's parity of the columns
-        for (int e = threadIdx.x; e < 32 * 16; e += 64 * NWV) {
+        for (int e = threadIdx.x; e < 32 * 16; e += 64 * CP_WAVES) {
             const int a = e >> 4, b = 2 * (e & 15) + par;
             out[(size_t)a * KW + b] = tsum(a, b);
         }
         return;
     }
-    for (int e = threadIdx.x; e < 32 * 32; e += 64 * NWV) {
+    for (int e = threadIdx.x; e < 32 * 32; e += 64 * CP_WAVES) {
         const int a = e >> 5, b = e & 31;
         out[(size_t)a * KW + b] = tsum(a, b);
     }
@@ -1459,9 +1448,6 @@ __device__ __forceinline__ void wcol_body(const Dims &d, const Bufs &b, const Dr
         blk -= nw;
     }
     // the loading-row variates of this iteration (generated chain), behind every other role
-#ifdef DCFM_DEV_NO_LAMGEN   // timing-only dev build: the variates of iterations > 3 are not drawn (stale, finite)
-    if (iter > 3) return;
-#endif
     if (blk < lg.b_total) lam_draws(d, lg, iter, blk * LAM_GEN_THREADS + (int)threadIdx.x, lg.b_total * LAM_GEN_THREADS);
 }
 
@@ -1763,11 +1749,7 @@ void launch_wcol(const Dims &d, const Bufs &b, const DrawsDev &dr, int64_t iter,
     if (lamgen && b.ldraw) lg = lam_gen_plan(d, b.ldraw);
     // W pass tiles: 64-row blocks up to one 128-row block per CU (the g = 32 share of c3: 256
     // blocks; 64-row ones measured 2.8 % faster there, 128-row ones faster at c3's 512)
-#ifdef DCFM_WCOL_WMODE
-    const int wmode = DCFM_WCOL_WMODE;   // dev A/B: forced block height
-#else
     const int wmode = (d.NP / 128) * d.G <= 256 ? 2 : 1;
-#endif
     const int nb = (ops ? d.G + xsum_blocks(d.G) : 0) + (colsum ? d.G : 0) + (wpass ? (d.NP / (64 * (3 - wmode))) * d.G : 0);
     if (nb + lg.b_total == 0) return;
     hipLaunchKernelGGL(k_wcol, dim3(nb + lg.b_total), dim3(256), 0, s, d, b, dr, iter, ops ? 1 : 0, colsum ? 1 : 0,
@@ -1807,29 +1789,27 @@ void launch_cpass(const Dims &d, const Bufs &b, hipStream_t s, const DrawsDev &d
     DeltaArgs da;
     da.delta_in = delta_in; da.tau_in = tau_in; da.delta_out = delta_out; da.tau_out = tau_out;
     da.iter = delta_iter;
-    const int ndel = (delta_in && d.kp == KP) ? cdiv(d.g, cp_waves<32>()) : 0;
+    const int ndel = (delta_in && d.kp == KP) ? cdiv(d.g, CP_WAVES) : 0;
     switch (d.kp) {
     case 32:
         // a few shards per rank: split the k columns by parity (k_cpass PS) below 128 blocks
         // (c3's g = 8 share, 88 blocks: +7 %; the g = 16 / 32 shares, 176 / 352: -4 / -2 %)
         if (grid.x < 128)
-            hipLaunchKernelGGL((k_cpass<32, true>), dim3(2 * grid.x + ndel), dim3(64 * cp_waves<32>()), 0, s, d, b.Y,
+            hipLaunchKernelGGL((k_cpass<32, true>), dim3(2 * grid.x + ndel), dim3(64 * CP_WAVES), 0, s, d, b.Y,
                                b.X, b.Z, b.C, b.E, dr, b.sall, da, ndel);
         else
-            hipLaunchKernelGGL((k_cpass<32, false>), dim3(grid.x + ndel), dim3(64 * cp_waves<32>()), 0, s, d, b.Y, b.X,
+            hipLaunchKernelGGL((k_cpass<32, false>), dim3(grid.x + ndel), dim3(64 * CP_WAVES), 0, s, d, b.Y, b.X,
                                b.Z, b.C, b.E, dr, b.sall, da, ndel);
         break;
     // wide: eta formed once (k_eta into W, free after k_zdraw) instead of in each of the shard's column
     // tiles from X and Z: their two 2 MB panels shared the XCD's L2 with the Y stream (c4: 358 MB)
     case 64:
-        if (DCFM_WIDE_ETA) launch_eta(d, b, b.W, s);
-        hipLaunchKernelGGL(k_cpass<64>, grid, dim3(256), 0, s, d, b.Y, DCFM_WIDE_ETA ? b.W : b.X, b.Z, b.C, b.E, dr,
-                           b.sall, da, 0);
+        launch_eta(d, b, b.W, s);
+        hipLaunchKernelGGL(k_cpass<64>, grid, dim3(256), 0, s, d, b.Y, b.W, b.Z, b.C, b.E, dr, b.sall, da, 0);
         break;
     default:
-        if (DCFM_WIDE_ETA) launch_eta(d, b, b.W, s);
-        hipLaunchKernelGGL(k_cpass<128>, grid, dim3(256), 0, s, d, b.Y, DCFM_WIDE_ETA ? b.W : b.X, b.Z, b.C, b.E, dr,
-                           b.sall, da, 0);
+        launch_eta(d, b, b.W, s);
+        hipLaunchKernelGGL(k_cpass<128>, grid, dim3(256), 0, s, d, b.Y, b.W, b.Z, b.C, b.E, dr, b.sall, da, 0);
         break;
     }
 }

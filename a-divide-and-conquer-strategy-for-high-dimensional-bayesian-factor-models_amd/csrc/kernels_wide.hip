@@ -516,8 +516,8 @@ __global__ __launch_bounds__(64) void k_lambda_w(
     // ---- blocked factorisation with the forward solve.  Look-ahead: block column J's trailing update
     //      of the next diagonal tile goes first, then that block's factor U = L^{-1} from its registers
     //      (chol_inv16_blk: 4 x 4 block steps, no LDS) with the rest of J's trailing MFMAs issued into
-    //      its four steps (la_step).  Round 6 replaced the pivot-by-pivot LDS factor (chol_inv16_hook,
-    //      16 round trips per block): k_lambda_w 369 -> 337 us at c4
+    //      its four steps (la_step).  Round 6 replaced a pivot-by-pivot LDS factor (16 round trips per
+    //      block): k_lambda_w 369 -> 337 us at c4
     {
         const d4 U0 = chol_inv16_blk(T[utix<NB>(0, 0)], lane, [](auto) {});
 #pragma unroll
@@ -855,6 +855,22 @@ template <int KW, class F>
 static void dispatch_tk(int K, F &&f) {   // tk in KW / 16 + 1 .. KW / 8
     dispatch_tk_impl<KW>((K + 7) / 8, f, std::make_integer_sequence<int, KW / 16>{});
 }
+// The launchers pick an instantiation from K while every buffer is padded to KW = d.kp = padded_width(K)
+// (dcfm_create); a K outside an instantiated range would launch nothing and report nothing.  So for every
+// wide K: ceil(K / 8) is in dispatch_tk's range of its width, ceil(K / 16) in launch_lambda's switch.
+constexpr bool every_wide_k(bool (*ok)(int K, int KW)) {
+    for (int K = KP + 1; K <= KP_MAX; ++K)
+        if (!ok(K, padded_width(K))) return false;
+    return true;
+}
+static_assert(every_wide_k([](int K, int KW) {
+    const int tk = (K + 7) / 8;
+    return (KW == 64 || KW == 128) && tk >= KW / 16 + 1 && tk <= KW / 8;
+}), "dispatch_tk misses a K in 33..128 at its padded width");
+static_assert(every_wide_k([](int K, int KW) {
+    const int nb = (K + 15) / 16;   // 3, 4: k_lambda_w<64, nb>; 5..8: k_lambda_w<128, nb>
+    return nb >= 3 && nb <= 8 && KW == (nb <= 4 ? 64 : 128);
+}), "launch_lambda's switch misses a K in 33..128 at its padded width");
 void launch_zdraw(const Dims &d, const Bufs &b, const DrawsDev &dr, int64_t iter, hipStream_t s) {
     WIDE_DISPATCH(d.kp, dispatch_tk<KW>(d.K, [&](auto T) {
         hipLaunchKernelGGL((k_zdraw<KW, decltype(T)::value>), dim3((d.NP / (16 * ZD_RT)) * d.G), dim3(256), 0, s, d, b.W,

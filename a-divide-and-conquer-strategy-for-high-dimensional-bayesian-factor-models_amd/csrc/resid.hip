@@ -39,9 +39,6 @@ __global__ __launch_bounds__(256) void k_resid(Dims d, const double *__restrict_
 #ifndef DCFM_RESID_RW
 #define DCFM_RESID_RW 4
 #endif
-#ifndef DCFM_RESID_LDSB
-#define DCFM_RESID_LDSB 0
-#endif
 #ifndef DCFM_RESID_WPE
 #define DCFM_RESID_WPE 2
 #endif
@@ -67,13 +64,11 @@ __global__ __launch_bounds__(64 * RW) __attribute__((amdgpu_waves_per_eu(DCFM_RE
 #pragma unroll
     for (int hp = 0; hp < 2; ++hp) ho[hp] = (j0 + 32 * hp < d.PP) ? 32 * hp : 0;   // invalid: re-read pair 0
     __syncthreads();
-#if !DCFM_RESID_LDSB
     d2 lb[4][4];   // B operands Lambda[j0 + 16h + c][8t + 2q .. +1], register-resident for the block
 #pragma unroll
     for (int h = 0; h < 4; ++h)
 #pragma unroll
         for (int t = 0; t < 4; ++t) lb[h][t] = *reinterpret_cast<const d2 *>(&Ls[jc(h)][8 * t + 2 * q]);
-#endif
     // Y of the block as a buffer resource: one 32-bit offset per row, the column tiles as offsets
     // (64-bit addresses per load cost two VGPRs each and made hipcc spill)
     const auto ysrc = __builtin_amdgcn_make_buffer_rsrc((void *)(Y + (size_t)m * d.NP * d.PP + j0), (short)0,
@@ -131,20 +126,10 @@ __global__ __launch_bounds__(64 * RW) __attribute__((amdgpu_waves_per_eu(DCFM_RE
         for (int h = 0; h < 4; ++h) acc[h] = d4{yA[h][0], yA[h][1], yA[h][2], yA[h][3]};   // invalid tiles: unused sums
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
-#if DCFM_RESID_LDSB   // B operands read from the LDS image per k-step (64 fewer VGPRs: 3 waves per SIMD)
-            d2 lt[4];
-#pragma unroll
-            for (int h = 0; h < 4; ++h) lt[h] = *reinterpret_cast<const d2 *>(&Ls[jc(h)][8 * t + 2 * q]);
-#pragma unroll
-            for (int h = 0; h < 4; ++h) acc[h] = mfma16x16x4(e[t][0], lt[h].x, acc[h]);
-#pragma unroll
-            for (int h = 0; h < 4; ++h) acc[h] = mfma16x16x4(e[t][1], lt[h].y, acc[h]);
-#else
 #pragma unroll
             for (int h = 0; h < 4; ++h) acc[h] = mfma16x16x4(e[t][0], lb[h][t].x, acc[h]);
 #pragma unroll
             for (int h = 0; h < 4; ++h) acc[h] = mfma16x16x4(e[t][1], lb[h][t].y, acc[h]);
-#endif
         }
         const int i0 = 16 * ch;
 #pragma unroll

@@ -50,6 +50,7 @@ __host__ __device__ constexpr int etile_index(int nbw, int R, int Cc) {
            (((R & 15) >> 2) & 1);
 }
 constexpr int ASM_KC = 16;            // k_assemble's k chunk (kext, LDB are multiples)
+inline int cdiv(int a, int b) { return (a + b - 1) / b; }   // launch grids
 
 struct Dims {
     int n, P, g, K, G;          // G = local shards
@@ -170,12 +171,12 @@ __host__ __device__ inline long long win_off(long long c, long long c0, long lon
     return (na > 0 ? na : 0) * (R1 - R0) + (b1 > b0 ? b1 - b0 : 0) * R1;
 }
 
-// launchers (kernels.hip)
+// launchers of the sweep (kernels.hip; K > 32 forwards to wide:: where the kernels differ)
 void launch_prep(const Dims &d, const Bufs &b, hipStream_t s);
 void launch_wpass(const Dims &d, const Bufs &b, hipStream_t s);
 void launch_zdraw(const Dims &d, const Bufs &b, const DrawsDev &dr, int64_t iter, hipStream_t s);
 void launch_xred(const Dims &d, const Bufs &b, hipStream_t s);
-// fused K <= 32 launches (kernels.hip: k_wcol, k_xdraw roles)
+// fused K <= 32 launches (kernels.hip: the roles of k_wcol, k_xdraw and k_cpass)
 // K <= 32: the Z operators + shard sum of A (ops), the previous iteration's column sums
 // (colsum) and the Y pass W with the Z draw of its rows (wpass: Z, Sp; needs ops) in one launch
 // (k_wcol); one rank also factors Xprec
@@ -216,6 +217,7 @@ void launch_resid_flagged(const Dims &d, const Bufs &b, const DrawsDev &dr, int6
 void launch_delta(const Dims &d, const Bufs &b, const DrawsDev &dr, int64_t iter,
                   const double *delta_in, const double *tau_in, double *delta_out,
                   double *tau_out, hipStream_t s);
+// assemble.hip: saved samples of a batch, their accumulation into Sigma, the output stripes
 void launch_save(const Dims &d, const Bufs &b, double *Lb, double *wsum, int slot, hipStream_t s);
 void launch_assemble(const Dims &d, const Bufs &b, const double *Lb, const double *wsum, int kext,
                      double inv_eff, hipStream_t s);
@@ -226,6 +228,7 @@ void launch_sigma_pack(const double *S, int p, int T0, int T1, int c0, int nc, d
 // recv + base[k]; Tb[0..nranks] are the ranks' tile-row boundaries (device arrays)
 void launch_sigma_unpack(const double *recv, int p, int c0, int nc, const int *Tb, const long long *base,
                          int nranks, double *out, hipStream_t s);
+// kernels.hip: eta = sqrt(rho) X + sqrt(1-rho) Z for every local shard (K > 32: once per iteration)
 void launch_eta(const Dims &d, const Bufs &b, double *eta_out, hipStream_t s);
 // sigma_err.hip: rows' sums of (Sigmaout - U U' - diag s) v, squares and truth squares
 // (partials [splits][p] in y / fro / tru; summed into out[0..p), out[p..2p), out[2p..3p))
@@ -243,6 +246,7 @@ inline size_t trace_scratch_doubles(int G) { return (size_t)G * TRACE_SLICES * 4
 void launch_trace(const Dims &d, const Bufs &b, const double *tau_cur, double *scratch, double *row, hipStream_t s);
 // init.hip: dc:68-87 initial state from Philox (iteration-0 counters), delta/tau buffer 0
 void launch_init_state(const Dims &d, const Bufs &b, hipStream_t s);
+// kernels.hip: one iteration's variates into the draw buffers (side-stream layouts)
 void launch_draws(const Dims &d, const DrawsDev &dr, int64_t iter, hipStream_t s);
 // NaN / Inf sentinel over the state (sets *flag = 1 if any value is non-finite)
 void launch_finite(const Dims &d, const Bufs &b, const double *tau_cur, int *flag, hipStream_t s);

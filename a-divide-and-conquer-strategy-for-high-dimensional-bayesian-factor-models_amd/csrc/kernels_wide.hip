@@ -1,8 +1,8 @@
 // Wide-factor kernels (K = 33 .. 128, padded width KW = 64 or 128) for the Gibbs
 // sweep of divideconquer.m:90-178.  Config c4 of BASELINE.json (p = 10,000,
 // n = 2,000, K = 100) runs here; K <= 32 uses the register-blocked narrow
-// kernels of kernels.hip.  The layout-generic kernels (k_wpass, k_cpass, k_xred,
-// k_asum, k_save, k_assemble) are shared and templated on KW in kernels.hip.
+// kernels of kernels.hip.  The layout-generic kernels (k_wpass, k_cpass, k_colsum, k_xred,
+// k_asum) are shared and templated on KW in kernels.hip; the assembly is assemble.hip.
 //
 // Kernel map (same dataflow as the narrow path)                reference lines
 //   k_gram     A_m = Lambda' diag(w) Lambda, 32x32 tiles, fp64 MFMA    dc:98-99,114-115
@@ -23,11 +23,10 @@
 #include "philox.h"
 #include "linalg.h"
 #include "tile_linalg.h"
+#include "delta.h"
 
 namespace dcfm {
 namespace wide {
-
-static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
 // ============================================================================
 // k_gram: A_m = (w o Lambda_m)' Lambda_m, 32x32 tile (ta, tb) per block; the GRAM_WAVES
@@ -161,9 +160,9 @@ __global__ __launch_bounds__(TILE_THREADS) void k_xchol(Dims d, const double *__
     tile::uut_store(Us, nb, N, d.sr, XM, KW, XM + (size_t)KW * KW);
 }
 
-// standard normals eps[i][kk], eps[i][kk+1] of a Z / X row (kk even)       dc:104,126
-__device__ __forceinline__ d2 row_normals(const Dims &d, const double *inj, bool live, int site, int mg, int i,
-                                          int kk, int64_t iter) {
+// standard normals eps[i][kk], eps[i][kk+1] of an X row (kk even) from its row inj of the draw
+// buffer (K > 32 always reads the buffers: injected draws or k_draws batches)      dc:126
+__device__ __forceinline__ d2 row_normals(const Dims &d, const double *inj, bool live, int kk) {
     d2 ev = {0.0, 0.0};
     if (!live || kk >= d.K) return ev;
     ev.x = inj[kk];
@@ -347,7 +346,7 @@ __global__ __launch_bounds__(64 * xd_waves<KW>()) void k_xdraw(Dims d, const dou
         TreeSum<d2> ts;                                  // the ranks' message sums, canonical tree
         for (int rk = 0; rk < d.nranks; ++rk) ts.push(*reinterpret_cast<const d2 *>(xall + rk * stride + (size_t)i * KW + kk));
         const d2 sv = ts.total();
-        const d2 ev = row_normals(d, nx, live, SITE_X, 0, i, kk, iter);
+        const d2 ev = row_normals(d, nx, live, kk);
 #pragma unroll
         for (int u = 0; u < MPW; ++u) {
             const int mt = wave * MPW + u;
@@ -668,157 +667,14 @@ __global__ __launch_bounds__(64) void k_lambda_w(
     }
 }
 
-// ============================================================================
-// block = (shard m, 32 columns); 8 row groups x 4 independent accumulators each.
-template <int KW>
-__global__ __launch_bounds__(256) void k_colsum(Dims d, const double *__restrict__ cpart, double *__restrict__ sloc) {
-    __shared__ double part[8][32];
-    const int m = blockIdx.x, k = 32 * blockIdx.y + (threadIdx.x & 31), grp = threadIdx.x >> 5;
-    const double *cp = cpart + (size_t)m * d.PP * KW + k;
-    double s4[4] = {0.0, 0.0, 0.0, 0.0};
-    int j = grp;
-    for (; j + 24 < d.P; j += 32) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) s4[u] += cp[(size_t)(j + 8 * u) * KW];
-    }
-    for (; j < d.P; j += 8) s4[0] += cp[(size_t)j * KW];
-    part[grp][threadIdx.x & 31] = (s4[0] + s4[1]) + (s4[2] + s4[3]);
-    __syncthreads();
-    if (threadIdx.x < 32) {
-        double tt = 0.0;
-#pragma unroll
-        for (int g2 = 0; g2 < 8; ++g2) tt += part[g2][threadIdx.x];
-        sloc[(size_t)m * KW + k] = tt;
-    }
-}
-
-// ============================================================================
-// k_delta: multiplicative-gamma-process chain for K in 33..128 (NV = KW/64
-// factors per lane: index l + 64 s).  Same algebra as the narrow kernel: every
-// shard's h >= 2 step reads shard 1's already-updated delta_h (quirk Q4), the
-// recomputed cumprod is the scalar factor F_h (dc:155-165).  (K == 1, quirk Q5,
-// is narrow-only.)
-// ============================================================================
-template <int NV>
-__device__ __forceinline__ void suffix_sum_nv(double (&v)[NV], int l) {
-    v[NV - 1] = wave_suffix_sum(v[NV - 1], l);
-    if (NV == 2) v[0] = wave_suffix_sum(v[0], l) + readlane_d(v[NV - 1], 0);
-}
-template <int NV>
-__device__ __forceinline__ void scan_prod_nv(double (&v)[NV], int l) {
-    v[0] = wave_scan_prod(v[0], l);
-    if (NV == 2) v[NV - 1] = wave_scan_prod(v[NV - 1], l) * readlane_d(v[0], 63);
-}
-// The chain over h as the narrow kernel runs it (kernels.hip delta_chain): with y_h = 1 / F_h the
-// recurrence is affine, y_{h+1} = alpha_h y_h + beta_h, alpha_h = b_h dold_h / G_h, beta_h = c_h dold_h /
-// G_h, c_h = (0.5 / dref_h) T_h, and dn_h = G_h y_h / (b_h y_h + c_h); the maps compose by a wave scan
-// (log2 steps) instead of K dependent steps of lane reads (measured 48.7 us per iteration at c4, a
-// serial chain on the critical path).  NV = 2: index l + 64 of the second slice composes with the
-// first slice's total map (lane 63).  Every term is positive: the reassociation moves the result
-// by a few ulps only (dc:157-163).
-__device__ __forceinline__ void affine_scan(double &A, double &B, int l) {   // inclusive, lane 0 first
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const double Ap = __shfl_up(A, o, 64), Bp = __shfl_up(B, o, 64);
-        if (l >= o) {
-            B = fma(A, Bp, B);
-            A = A * Ap;
-        }
-    }
-}
-template <int NV>
-__device__ __forceinline__ void delta_chain_nv(const Dims &d, int l, const double (&T)[NV], const double (&G)[NV],
-                               const double (&idold)[NV], const double (&idref)[NV], double (&dnew)[NV]) {
-    double bh[NV], c[NV], A[NV], B[NV];
-    bool act[NV];
-#pragma unroll
-    for (int s = 0; s < NV; ++s) {
-        const int idx = l + 64 * s;
-        act[s] = idx < d.K;
-        bh[s] = (idx == 0) ? d.bd1 : d.bd2;
-        c[s] = (0.5 * idref[s]) * T[s];
-        const double inv = 1.0 / (idold[s] * G[s]);              // dold_h / G_h
-        A[s] = act[s] ? bh[s] * inv : 1.0;                        // identity map on idle indices
-        B[s] = act[s] ? c[s] * inv : 0.0;
-        affine_scan(A[s], B[s], l);
-    }
-    if (NV == 2) {   // the second slice after the whole first one
-        const double A0 = readlane_d(A[0], 63), B0 = readlane_d(B[0], 63);
-        B[NV - 1] = fma(A[NV - 1], B0, B[NV - 1]);
-        A[NV - 1] = A[NV - 1] * A0;
-    }
-    double yin[NV];
-#pragma unroll
-    for (int s = 0; s < NV; ++s) yin[s] = A[s] + B[s];            // y_{idx+1} (y_0 = 1)
-#pragma unroll
-    for (int s = 0; s < NV; ++s) {
-        const double yprev = __shfl_up(yin[s], 1, 64);
-        const double y = (l == 0) ? (s == 0 ? 1.0 : readlane_d(yin[0], 63)) : yprev;   // y_idx
-        dnew[s] = act[s] ? G[s] * y / fma(bh[s], y, c[s]) : 1.0;
-    }
-}
-
-// one wave = global shard m, lane t (< 64 active)
-template <int KW>
-__device__ __forceinline__ void delta_shard_w(const Dims &d, const double *__restrict__ sall,
-                                              const double *__restrict__ delta_in, const double *__restrict__ tau_in,
-                                              double *__restrict__ delta_out, double *__restrict__ tau_out,
-                                              const DrawsDev &dr, int64_t iter, int m, int t) {
-    constexpr int NV = KW / 64;
-    if (t < 64) {
-        const int l = t;
-        double d0[NV], T0[NV], G0[NV], id0[NV], d0new[NV];
-#pragma unroll
-        for (int s = 0; s < NV; ++s) {
-            const int idx = l + 64 * s;
-            const bool act = idx < d.K;
-            d0[s] = act ? delta_in[idx] : 1.0;
-            T0[s] = act ? tau_in[idx] * sall[idx] : 0.0;
-            G0[s] = act ? delta_G(d, dr, iter, 0, idx) : 1.0;
-            id0[s] = 1.0 / d0[s];
-        }
-        suffix_sum_nv<NV>(T0, l);
-        delta_chain_nv<NV>(d, l, T0, G0, id0, id0, d0new);   // shard 1, its own pre-update delta_h
-        double dm[NV];
-#pragma unroll
-        for (int s = 0; s < NV; ++s) dm[s] = d0new[s];
-        if (m != 0) {
-            double Tm[NV], Gm[NV], idold[NV], idref[NV];
-#pragma unroll
-            for (int s = 0; s < NV; ++s) {
-                const int idx = l + 64 * s;
-                const bool act = idx < d.K;
-                const size_t o = (size_t)m * KW + idx;
-                const double dold = act ? delta_in[o] : 1.0;
-                Tm[s] = act ? tau_in[o] * sall[o] : 0.0;
-                Gm[s] = act ? delta_G(d, dr, iter, m, idx) : 1.0;
-                idold[s] = 1.0 / dold;
-                idref[s] = (idx == 0) ? idold[s] : 1.0 / d0new[s];   // delta(1,:,m) | delta(h) (Q4)
-            }
-            suffix_sum_nv<NV>(Tm, l);
-            delta_chain_nv<NV>(d, l, Tm, Gm, idold, idref, dm);
-        }
-        double tm[NV];
-#pragma unroll
-        for (int s = 0; s < NV; ++s) tm[s] = (l + 64 * s < d.K) ? dm[s] : 1.0;
-        scan_prod_nv<NV>(tm, l);                                     // tauh = cumprod(delta)
-#pragma unroll
-        for (int s = 0; s < NV; ++s) {
-            const int idx = l + 64 * s;
-            const bool act = idx < d.K;
-            const size_t o = (size_t)m * KW + idx;
-            delta_out[o] = act ? dm[s] : delta_in[o];
-            tau_out[o] = act ? tm[s] : tau_in[o];
-        }
-    }
-}
-
+// k_delta: the delta / tau chain for K in 33..128, one block (one wave) per global shard with
+// KW / 64 factors per lane (delta.h)                                              dc:155-165
 template <int KW>
 __global__ __launch_bounds__(64) void k_delta(Dims d, const double *__restrict__ sall,
                                                const double *__restrict__ delta_in, const double *__restrict__ tau_in,
                                                double *__restrict__ delta_out, double *__restrict__ tau_out,
                                                DrawsDev dr, int64_t iter) {
-    delta_shard_w<KW>(d, sall, delta_in, tau_in, delta_out, tau_out, dr, iter, blockIdx.x, threadIdx.x);
+    delta_shard<KW>(d, sall, delta_in, tau_in, delta_out, tau_out, dr, iter, blockIdx.x, threadIdx.x);
 }
 
 // ============================================================================

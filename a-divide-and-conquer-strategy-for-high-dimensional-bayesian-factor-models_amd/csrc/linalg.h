@@ -49,15 +49,6 @@ __device__ __forceinline__ void static_for(F &&f) {
     static_for_impl(f, std::make_integer_sequence<int, N>{});
 }
 
-// value of lane LANE of this lane's 16-lane DPP row (v_mov_b32_dpp row_newbcast)
-template <int LANE>
-__device__ __forceinline__ double bcast16(double v) {
-    static_assert(LANE >= 0 && LANE < 16, "row_newbcast lane");
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), 0x150 + LANE, 0xF, 0xF, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), 0x150 + LANE, 0xF, 0xF, false);
-    return __hiloint2double(hi, lo);
-}
-
 // Canonical shard sum, independent of the rank count: sum_{m < n} x_m evaluated as the
 // left-complete binary tree T(0, n) = T(0, h) + T(h, n - h), h = the largest power of two
 // below n.  A rank's G consecutive shards (G a power of two, offset a multiple of G) are
@@ -116,15 +107,6 @@ __device__ __forceinline__ double tree_sum(const double *__restrict__ src, int n
     return tree_sum_f<double>(n, [&](int k) { return src[(size_t)k * stride]; });
 }
 
-// Agent-scope (all XCDs) coherent access for data handed between blocks of one launch:
-// relaxed atomics bypass the non-coherent per-XCD L2 copies (sc1), no L2 flush needed.
-__device__ __forceinline__ void st_agent(double *p, double v) {
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ double ld_agent(const double *p) {
-    return __hip_atomic_load(const_cast<double *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 // 1/sqrt(x) to full fp64 precision: hardware estimate + 2 Newton steps
 __device__ __forceinline__ double rsqrt_f64(double x) {
     double y = __builtin_amdgcn_rsq(x);
@@ -170,16 +152,6 @@ __device__ __forceinline__ double wave_suffix_sum(double v, int l) {
         if (l + o < 64) v += u;
     }
     return v;
-}
-
-// standard gamma of the delta site, h = 0-based factor index (dc:158,163): the injected
-// buffer, or — generated draws — the counter-addressed Philox variate itself (the value
-// k_draws writes), so the delta chain never depends on which draw-batch slot holds its
-// iteration (k_wcol runs iteration t's chain during iteration t+1)
-__device__ inline double delta_G(const Dims &d, const DrawsDev &dr, int64_t iter, int mg, int h) {
-    if (d.inject) return dr.Gdelta[((size_t)(iter - dr.first_iter) * d.g + mg) * d.K + h];
-    const double shape = (h == 0) ? d.ad1 + 0.5 * d.P * d.K : d.ad2 + 0.5 * d.P * (d.K - h);
-    return Rng(d.seed).gamma(shape, SITE_DELTA, (uint32_t)mg, 0, (uint32_t)h, (uint32_t)iter);
 }
 
 // eta = sqrt(rho) X + sqrt(1-rho) Z    (dc:81,133) — one definition for every use, with the
@@ -263,7 +235,6 @@ __device__ __forceinline__ void chol_rows_fwd(double (&q)[KP], double *Lp, int r
 __host__ __device__ constexpr int pb2(int j) { return 64 * j - 2 * j * (j - 1); }
 constexpr int PACK2 = pb2(KP / 2);
 constexpr int P2STRIDE = PACK2 + 2 * KP;
-__device__ __forceinline__ int p2idx(int c, int k) { return pb2(k >> 1) + 2 * (c - (k & ~1)) + (k & 1); }
 
 template <bool FWD>
 __device__ __forceinline__ void chol2_rows(double (&q)[KP], double *P, int r, bool upper, double bv,
@@ -580,42 +551,6 @@ __device__ __forceinline__ d4 mfma_tile32(const double (*A)[KP + 1], const doubl
         acc = mfma16x16x4(a, b, acc);
     }
     return acc;
-}
-
-// U = L^{-1} from the pair-packed image P of chol2_rows: lane j (threads 0..31)
-// forward-substitutes column j; result in Us[a][j].
-__device__ __forceinline__ void lower_inverse2(const double *P, double (*Us)[KP + 1], int t) {
-    if (t >= KP) return;
-    const int j = t;
-    double u[KP];
-#pragma unroll
-    for (int a = 0; a < KP; ++a) {
-        double acc = (a == j) ? 1.0 : 0.0;
-#pragma unroll
-        for (int b = 0; b < a; ++b) acc -= P[pb2(b >> 1) + 2 * (a - (b & ~1)) + (b & 1)] * u[b];
-        u[a] = acc * P[PACK2 + a];
-    }
-#pragma unroll
-    for (int a = 0; a < KP; ++a) Us[a][j] = u[a];
-}
-
-// ----------------------------------------------------------------------------
-// U = L^{-1} from the LDS image Lt of a lower Cholesky factor (chol_rows): lane j
-// (threads 0..31) forward-substitutes column j; result in Us[a][j].
-// ----------------------------------------------------------------------------
-__device__ __forceinline__ void lower_inverse(const double (*Lt)[LS], double (*Us)[KP + 1], int t) {
-    if (t >= KP) return;
-    const int j = t;
-    double u[KP];
-#pragma unroll
-    for (int a = 0; a < KP; ++a) {
-        double acc = (a == j) ? 1.0 : 0.0;
-#pragma unroll
-        for (int b = 0; b < a; ++b) acc -= Lt[b][a] * u[b];    // L[a][b] = Lt[b][a]
-        u[a] = acc * Lt[a][KP];
-    }
-#pragma unroll
-    for (int a = 0; a < KP; ++a) Us[a][j] = u[a];
 }
 
 }  // namespace dcfm

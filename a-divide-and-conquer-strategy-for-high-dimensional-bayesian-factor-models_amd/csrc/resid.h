@@ -16,6 +16,7 @@
 #pragma once
 #include "dcfm_internal.h"
 #include "linalg.h"
+#include "handoff.h"
 
 namespace dcfm {
 

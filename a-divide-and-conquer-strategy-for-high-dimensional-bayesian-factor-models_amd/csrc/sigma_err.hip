@@ -34,7 +34,6 @@ constexpr int ERR_RMAX = 32;
 #ifndef ERR_NT
 #define ERR_NT 2   // 32 x 32 tiles per pipelined step
 #endif
-static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
 // stored element (a, b), a >= b: does this rank own it (tile row a / 128 in [T0, T1))?
 __device__ __forceinline__ bool owns(int a, int T0, int T1) {

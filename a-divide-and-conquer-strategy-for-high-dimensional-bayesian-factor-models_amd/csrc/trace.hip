@@ -19,7 +19,7 @@
 // host all-reduces).  Cost when enabled: one read of Lambda (G x PP x KW doubles; 5 MB at c3), off
 // by default.
 #include "dcfm_internal.h"
-#include "linalg.h"
+#include "handoff.h"
 
 namespace dcfm {
 
@@ -51,16 +51,9 @@ __global__ __launch_bounds__(256) void k_trace_part(const double *__restrict__ L
         __syncthreads();
     }
     if (t < 4) st_agent(part + ((size_t)m * TRACE_SLICES + sl) * 4 + t, red[t][0]);
-    // the shard's last slice block folds the slices (agent-scope hand-off, kernels.hip signal_count)
-    __shared__ unsigned last;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (t == 0) {
-        last = __hip_atomic_fetch_add(ticket + m, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == TRACE_SLICES - 1;
-        if (last) __hip_atomic_store(ticket + m, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // next iteration
-    }
-    __syncthreads();
-    if (!last || t >= 4) return;
+    // the shard's last slice block folds the slices (handoff.h)
+    __shared__ unsigned flag;
+    if (!last_arrival(ticket + m, TRACE_SLICES, &flag) || t >= 4) return;
     double acc = 0.0;
     for (int k = 0; k < TRACE_SLICES; ++k) acc += ld_agent(part + ((size_t)m * TRACE_SLICES + k) * 4 + t);
     row[(size_t)m * 4 + t] = acc;

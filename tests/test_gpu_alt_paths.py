@@ -46,7 +46,9 @@ UNFUSED, ONE_STREAM = 0x2, 0x4
 
 @pytest.mark.parametrize("flags,case", [(UNFUSED, "basic"), (UNFUSED, "K30"), (ONE_STREAM, "K30"),
                                         (UNFUSED | ONE_STREAM, "basic"),
-                                        (UNFUSED, "g5_odd_chunk"), (UNFUSED, "g10_odd_chunk")])
+                                        (UNFUSED, "g5_odd_chunk"), (UNFUSED, "g10_odd_chunk"),
+                                        # the stand-alone narrow k_delta in the K = 1 (Q5) and shard-1 (Q4) regimes
+                                        (UNFUSED, "K1_g3_cumprod_dim3"), (UNFUSED, "K2_g3_shard1_delta")])
 def test_alternate_path_parity(flags, case):
     import test_gpu_parity as T
     if case not in T.CASES:

@@ -65,7 +65,8 @@ __device__ __forceinline__ double u01_53(uint32_t hi, uint32_t lo) {
 // ---- transcendental kernels for arguments produced by u01_53 (u in [2^-53, 1]) ----
 // The library log / sqrt / sincospi handle every IEEE case (~350 instructions per
 // Box-Muller pair with Philox); these cover exactly the uniforms' range in ~1/3 of
-// that, to within a few ulp (the variates are checked statistically, tests/test_gpu_rng.py).
+// that, to within a few ulp (the variates' distribution is checked by tests/test_gpu_rng.py, their
+// values one by one against an extended-precision host reference by tests/test_gpu_rng_exact.py).
 
 // log(u), u in [2^-106, 1] (a uniform or the product of two): u = 2^e m, m in [sqrt(1/2), sqrt(2)), log m = 2 atanh(s),
 // s = (m-1)/(m+1), |s| <= 0.1716: series to s^23 (truncation < 1e-18 relative)

@@ -5,8 +5,8 @@ addressed by its counter (site, shard, row, index, iteration; csrc/philox.h), so
 generated mode must be BITWISE the chain run in injected mode on the variates dcfm_rng_fill
 produces at those counters (row = i / 32, index = i % 32: a fill of rows x 32 is the row's
 first 32 indices; dcfm_rng_fill_rows with width K reaches the wide kernels' indices up to 127).
-This pins the in-place draws of both paths to the counter scheme the RNG tests check statistically
-(tests/test_gpu_rng.py).
+This pins the in-place draws of both paths to the counter scheme the RNG tests check: statistically
+(tests/test_gpu_rng.py) and value by value (tests/test_gpu_rng_exact.py).
 """
 import numpy as np
 import pytest

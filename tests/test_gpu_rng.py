@@ -1,6 +1,9 @@
 """On-device Philox normal / gamma variates (dc:104,126,142,150,158,163,170 sites):
 moments and Kolmogorov-Smirnov against the exact distributions, at every gamma
-shape the sweep uses, plus counter-addressing properties."""
+shape the sweep uses, plus counter-addressing properties.
+
+This file checks the variates' DISTRIBUTION; tests/test_gpu_rng_exact.py checks their VALUES, one by
+one against the host reference oracle/philox_ref.py at the same counters."""
 import numpy as np
 import pytest
 from scipy import stats

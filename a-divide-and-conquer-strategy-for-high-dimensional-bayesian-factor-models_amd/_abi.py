@@ -27,6 +27,12 @@ DCFM_FLAG_FLAT_PRIORITY = 0x8  # default priority for every stream
 DCFM_FLAG_COMM_SELF = 0x20   # one rank on the collective path with a real 1-rank RCCL communicator
 DCFM_FLAG_EXACT_RESIDUAL = 0x10  # ps / omega from the direct residual (dc:169), one more Y pass
 DCFM_FLAG_GUARD_ALL = 0x40       # the SS-identity guard rejects every row (its residual fallback, tests)
+DCFM_FLAG_SIGMA_M2 = 0x80        # accumulate the second moment of the per-sample Sigma (M2 / SD read-out)
+# dcfm_get_sigma_moment[_cols]'s `which`
+DCFM_SIGMA_MEAN = 0
+DCFM_SIGMA_M2 = 1
+DCFM_SIGMA_SD = 2
+SIGMA_MOMENTS = {"mean": DCFM_SIGMA_MEAN, "m2": DCFM_SIGMA_M2, "sd": DCFM_SIGMA_SD}
 
 KERNEL_IDS = {
     "k_prep": 0, "k_wpass": 1, "k_zdraw": 2, "k_xred": 3, "k_xdraw": 4, "k_cpass": 5,
@@ -40,7 +46,7 @@ EXPORTS = (
     "dcfm_create", "dcfm_destroy", "dcfm_last_error", "dcfm_abi_version",
     "dcfm_comm_unique_id", "dcfm_comm_init", "dcfm_comm_init_loopback", "dcfm_set_data", "dcfm_set_state",
     "dcfm_set_draws", "dcfm_run", "dcfm_synchronize", "dcfm_get_state", "dcfm_get_state_raw", "dcfm_get_sigma",
-    "dcfm_get_sigma_cols", "dcfm_sigma_block",
+    "dcfm_get_sigma_cols", "dcfm_sigma_block", "dcfm_get_sigma_moment_cols", "dcfm_get_sigma_moment",
     "dcfm_saved_samples", "dcfm_sigma_error", "dcfm_set_profiling", "dcfm_set_profiling_mask", "dcfm_set_profiling_stride", "dcfm_get_kernel_stats",
     "dcfm_kernel_name",
     "dcfm_rng_fill", "dcfm_rng_fill_rows", "dcfm_set_data_raw", "dcfm_get_data", "dcfm_count_nonzero_columns",
@@ -111,6 +117,8 @@ def load_library(path: Path | None = None):
         "dcfm_get_sigma": (C.c_int, [vp, _DP]),
         "dcfm_get_sigma_cols": (C.c_int, [vp, C.c_int64, C.c_int64, _DP]),
         "dcfm_sigma_block": (C.c_int, [vp, C.POINTER(C.c_int64)]),
+        "dcfm_get_sigma_moment_cols": (C.c_int, [vp, C.c_int32, C.c_int64, C.c_int64, _DP]),
+        "dcfm_get_sigma_moment": (C.c_int, [vp, C.c_int32, _DP]),
         "dcfm_saved_samples": (C.c_int64, [vp]),
         "dcfm_sigma_error": (C.c_int, [vp, _DP, C.c_int32, _DP, C.c_int32, C.c_uint64, _DP]),
         "dcfm_set_profiling": (C.c_int, [vp, C.c_int]),

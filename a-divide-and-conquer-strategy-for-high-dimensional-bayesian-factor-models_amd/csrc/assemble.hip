@@ -10,11 +10,13 @@ namespace dcfm {
 
 // ============================================================================
 // saved samples: Lb[(mg*P + j)][slot*K + k] = Lambda, wsum += omega         dc:180-186
+// M2 (DCFM_FLAG_SIGMA_M2): also the sample's own omega, wslot[(mg*P + j)][slot] of B slots
 // ============================================================================
+template <bool M2>
 __global__ __launch_bounds__(256) void k_save(Dims d, const double *__restrict__ Lam,
                                               const double *__restrict__ omega,
                                               double *__restrict__ Lb, double *__restrict__ wsum,
-                                              int LDB, int slot) {
+                                              int LDB, int slot, double *__restrict__ wslot, int B) {
     const size_t total = (size_t)d.G * d.P * d.K;
     for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < total;
          e += (size_t)gridDim.x * blockDim.x) {
@@ -23,7 +25,11 @@ __global__ __launch_bounds__(256) void k_save(Dims d, const double *__restrict__
         const int j = jm % d.P, m = jm / d.P;
         const size_t a = (size_t)(d.shard0 + m) * d.P + j;
         Lb[a * LDB + (size_t)slot * d.K + k] = Lam[((size_t)m * d.PP + j) * d.kp + k];
-        if (k == 0) wsum[a] += omega[(size_t)m * d.PP + j];
+        if (k == 0) {
+            const double w = omega[(size_t)m * d.PP + j];
+            wsum[a] += w;
+            if (M2) wslot[a * B + slot] = w;
+        }
     }
 }
 
@@ -201,8 +207,19 @@ __global__ __launch_bounds__(256, 2) void k_assemble(Dims d, const double *__res
 // the symmetrisation is this mirror).  One rank owns everything: the windows are then the
 // dense p x nc column-major stripe.  32x32 tiles: Sigma(r, c) = S(r, c) for r >= c (read
 // along c, transposed through LDS), S(c, r) for r < c (read along r).
-__global__ __launch_bounds__(256) void k_sigma_pack(const double *__restrict__ S, int p, int T0, int T1, int c0,
-                                                    int nc, double *__restrict__ out) {
+// WHICH (DCFM_SIGMA_*): the mean S, the second moment S2, or the posterior standard deviation
+// sqrt(max(0, rs S2 - (rs S)^2)) formed here from both (rs = effsamp / saved samples), so
+// neither matrix leaves the device to be combined.
+template <int WHICH>
+__global__ __launch_bounds__(256) void k_sigma_pack(const double *__restrict__ S, const double *__restrict__ S2,
+                                                    double rs, int p, int T0, int T1, int c0, int nc,
+                                                    double *__restrict__ out) {
+    auto at = [&](size_t o) {
+        if (WHICH == 0) return S[o];
+        if (WHICH == 1) return S2[o];
+        const double m = rs * S[o];
+        return sqrt(fmax(0.0, fma(rs, S2[o], -m * m)));
+    };
     __shared__ double lo[32][33];
     const int R0 = min(p, T0 * ASM_TILE), R1 = min(p, T1 * ASM_TILE);
     const int r0 = blockIdx.x * 32, cb = c0 + blockIdx.y * 32;
@@ -212,7 +229,7 @@ __global__ __launch_bounds__(256) void k_sigma_pack(const double *__restrict__ S
     if (need_lo) {
         for (int yy = ty; yy < 32; yy += 8) {      // rows r = r0 + yy, columns c = cb + tx
             const int r = r0 + yy, c = cb + tx;
-            lo[yy][tx] = (r >= R0 && r < R1 && c < c0 + nc && r >= c) ? S[sig_off(r, c, T0)] : 0.0;
+            lo[yy][tx] = (r >= R0 && r < R1 && c < c0 + nc && r >= c) ? at(sig_off(r, c, T0)) : 0.0;
         }
     }
     __syncthreads();
@@ -221,7 +238,7 @@ __global__ __launch_bounds__(256) void k_sigma_pack(const double *__restrict__ S
         if (c >= c0 + nc || r >= R1) continue;
         const long long wl = win_lo(c, R0, R1);
         if (r < wl) continue;
-        const double v = (r >= c) ? lo[tx][yy] : (need_up ? S[sig_off(c, r, T0)] : 0.0);
+        const double v = (r >= c) ? lo[tx][yy] : (need_up ? at(sig_off(c, r, T0)) : 0.0);
         out[win_off(c, c0, R0, R1) + (r - wl)] = v;
     }
 }
@@ -245,10 +262,14 @@ __global__ __launch_bounds__(256) void k_sigma_unpack(const double *__restrict__
 // ============================================================================
 // launchers
 // ============================================================================
-void launch_save(const Dims &d, const Bufs &b, double *Lb, double *wsum, int slot, hipStream_t s) {
+void launch_save(const Dims &d, const Bufs &b, double *Lb, double *wsum, int slot, hipStream_t s, double *wslot,
+                 int B) {
     const size_t total = (size_t)d.G * d.P * d.K;
     const int grid = (int)std::min<size_t>((total + 255) / 256, 4096);
-    hipLaunchKernelGGL(k_save, dim3(grid), dim3(256), 0, s, d, b.Lam, b.omega, Lb, wsum, b.LDB, slot);
+    if (wslot)
+        hipLaunchKernelGGL(k_save<true>, dim3(grid), dim3(256), 0, s, d, b.Lam, b.omega, Lb, wsum, b.LDB, slot, wslot, B);
+    else
+        hipLaunchKernelGGL(k_save<false>, dim3(grid), dim3(256), 0, s, d, b.Lam, b.omega, Lb, wsum, b.LDB, slot, wslot, B);
 }
 void launch_assemble(const Dims &d, const Bufs &b, const double *Lb, const double *wsum, int kext,
                      double inv_eff, hipStream_t s) {
@@ -256,10 +277,14 @@ void launch_assemble(const Dims &d, const Bufs &b, const double *Lb, const doubl
     hipLaunchKernelGGL(k_assemble, dim3(b.ntiles), dim3(ASM_THREADS), 0, s, d, Lb, b.LDB, kext, wsum, inv_eff,
                        b.tiles, b.T0, b.Sigma);
 }
-void launch_sigma_pack(const double *S, int p, int T0, int T1, int c0, int nc, double *out, hipStream_t s) {
+void launch_sigma_pack(const double *S, const double *S2, int which, double rs, int p, int T0, int T1, int c0,
+                       int nc, double *out, hipStream_t s) {
     const int R1 = std::min(p, T1 * ASM_TILE);
     if (nc <= 0 || R1 <= 0 || T1 <= T0) return;
-    hipLaunchKernelGGL(k_sigma_pack, dim3(cdiv(R1, 32), cdiv(nc, 32)), dim3(256), 0, s, S, p, T0, T1, c0, nc, out);
+    const dim3 grid(cdiv(R1, 32), cdiv(nc, 32));
+    if (which == 0) hipLaunchKernelGGL(k_sigma_pack<0>, grid, dim3(256), 0, s, S, S2, rs, p, T0, T1, c0, nc, out);
+    else if (which == 1) hipLaunchKernelGGL(k_sigma_pack<1>, grid, dim3(256), 0, s, S, S2, rs, p, T0, T1, c0, nc, out);
+    else hipLaunchKernelGGL(k_sigma_pack<2>, grid, dim3(256), 0, s, S, S2, rs, p, T0, T1, c0, nc, out);
 }
 void launch_sigma_unpack(const double *recv, int p, int c0, int nc, const int *Tb, const long long *base,
                          int nranks, double *out, hipStream_t s) {

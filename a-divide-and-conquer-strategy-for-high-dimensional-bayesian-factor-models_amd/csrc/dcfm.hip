@@ -239,6 +239,11 @@ static int alloc_buffers(dcfm_handle *h) {
         b.T1 = h->Tb[c.rank + 1];
     }
     TRY(dalloc(h, &b.Sigma, (size_t)(tri(b.T1) - tri(b.T0)) * ASM_TILE * ASM_TILE));
+    if (c.flags & DCFM_FLAG_SIGMA_M2) {   // second moment beside the mean, and each saved sample's own omega
+        TRY(dalloc(h, &b.Sigma2, (size_t)(tri(b.T1) - tri(b.T0)) * ASM_TILE * ASM_TILE));
+        TRY(dalloc(h, &b.wslot[0], p * (size_t)h->B));
+        TRY(dalloc(h, &b.wslot[1], p * (size_t)h->B));
+    }
     // the generated fused chain: k_wcol's LAMGEN blocks draw the loading-row variates into b.ldraw
     // each iteration (lam_draws)
     if (h->fused && !d.inject) TRY(dalloc(h, &b.ldraw, (size_t)lam_gen_doubles(d)));
@@ -369,6 +374,9 @@ static int flush_batch(dcfm_handle *h) {
                                 h->sasm);
         if (rc == DCFM_OK)
             rc = coll_allgather(h, CH_ASM, b.wsum[lb] + (size_t)d.rank * rows, b.wsum[lb], rows, h->sasm);
+        if (rc == DCFM_OK && b.Sigma2)
+            rc = coll_allgather(h, CH_ASM, b.wslot[lb] + (size_t)d.rank * rows * h->B, b.wslot[lb], rows * h->B,
+                                h->sasm);
         if (!h->loop) NCCLC(h, ncclGroupEnd());
         if (rc) return rc;
     }
@@ -384,6 +392,8 @@ static int flush_batch(dcfm_handle *h) {
     {
         KTimer t(h, DCFM_K_ASSEMBLE, h->sasm);
         launch_assemble(d, b, b.Lb[lb], b.wsum[lb], kext, 1.0 / effsamp, h->sasm);
+        // DCFM_FLAG_SIGMA_M2: the batch's samples one by one into the second moment
+        if (b.Sigma2) launch_assemble_m2(d, b, b.Lb[lb], b.wslot[lb], h->batch, h->B, 1.0 / effsamp, h->sasm);
     }
     HIPC(h, hipGetLastError());
     HIPC(h, hipMemsetAsync(b.wsum[lb], 0, (size_t)d.p * sizeof(double), h->sasm));   // k_save adds into it
@@ -458,7 +468,7 @@ static int save_sample(dcfm_handle *h, int64_t it) {
         HIPC(h, hipStreamWaitEvent(s, h->e_free[h->lb], 0));
         h->asm_pending[h->lb] = false;
     }
-    { KTimer t(h, DCFM_K_SAVE, s); launch_save(h->d, b, b.Lb[h->lb], b.wsum[h->lb], h->batch, s); }
+    { KTimer t(h, DCFM_K_SAVE, s); launch_save(h->d, b, b.Lb[h->lb], b.wsum[h->lb], h->batch, s, b.wslot[h->lb], h->B); }
     HIPC(h, hipGetLastError());
     h->batch += 1;
     h->saved += 1;

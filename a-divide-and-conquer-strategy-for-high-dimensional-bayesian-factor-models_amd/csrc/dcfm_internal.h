@@ -23,6 +23,8 @@
 //   sloc   [G][KW], sall [g][KW]  column sums (all-gathered)
 //   Lb     [2][p][LDB]   saved Lambda rows of an assembly batch (double-buffered), sample s at cols s*K..
 //   wsum   [2][p]        sum of saved omega of the batch
+//   wslot  [2][p][B]     DCFM_FLAG_SIGMA_M2: each saved sample's own omega (slot s of row a at a*B + s)
+//   Sigma2 [ntiles][128][128]  DCFM_FLAG_SIGMA_M2: second moment of the per-sample Sigma, laid out as Sigma
 //   Sigma  [ntiles][128][128]  this rank's block of the lower triangle of Sigmaout, tile-packed:
 //                        rank r owns the contiguous tile rows [T0, T1) (balanced by tile count,
 //                        sigma_split), tile (ti, tj), tj <= ti, at index tri(ti) - tri(T0) + tj,
@@ -111,6 +113,7 @@ struct Bufs {
     double *ldraw;                     // LamDraws of the generated fused chain (lam_gen_plan), else null
     double *W, *A, *ZM, *Sp, *xin, *xall, *C, *E, *cpart, *sloc, *sall;
     double *Lb[2], *wsum[2], *Sigma;
+    double *wslot[2], *Sigma2;         // DCFM_FLAG_SIGMA_M2: per-sample omega of a batch, second moment; else null
     double *xa, *xa_all, *XM;          // per-rank sum of A, gathered sums, X-draw operators
     double *xpart;                     // k_wcol chunk sums of A (xsum_blocks(G) x KP x KP)
     unsigned *ticket;                  // k_wcol last-arrival ticket (0 between launches)
@@ -218,12 +221,20 @@ void launch_delta(const Dims &d, const Bufs &b, const DrawsDev &dr, int64_t iter
                   const double *delta_in, const double *tau_in, double *delta_out,
                   double *tau_out, hipStream_t s);
 // assemble.hip: saved samples of a batch, their accumulation into Sigma, the output stripes
-void launch_save(const Dims &d, const Bufs &b, double *Lb, double *wsum, int slot, hipStream_t s);
+// (wslot, DCFM_FLAG_SIGMA_M2: also the sample's omega into slot `slot` of B)
+void launch_save(const Dims &d, const Bufs &b, double *Lb, double *wsum, int slot, hipStream_t s,
+                 double *wslot = nullptr, int B = 0);
 void launch_assemble(const Dims &d, const Bufs &b, const double *Lb, const double *wsum, int kext,
                      double inv_eff, hipStream_t s);
+// assemble_m2.hip: b.Sigma2 += (1 / effsamp) sum over the batch's nslots samples of the squared
+// per-sample Sigma (Lb slots of K columns, wslot [p][B] the samples' omega)
+void launch_assemble_m2(const Dims &d, const Bufs &b, const double *Lb, const double *wslot, int nslots, int B,
+                        double inv_eff, hipStream_t s);
 // column stripe [c0, c0 + nc) of Sigmaout from a rank's tile-packed block (tile rows [T0, T1)):
-// the rank's packed windows (win_lo / win_off; with one rank = the dense p x nc stripe)
-void launch_sigma_pack(const double *S, int p, int T0, int T1, int c0, int nc, double *out, hipStream_t s);
+// the rank's packed windows (win_lo / win_off; with one rank = the dense p x nc stripe).
+// which (DCFM_SIGMA_*): 0 the mean S, 1 the second moment S2, 2 sqrt(max(0, rs S2 - (rs S)^2))
+void launch_sigma_pack(const double *S, const double *S2, int which, double rs, int p, int T0, int T1, int c0,
+                       int nc, double *out, hipStream_t s);
 // root of the gather: the dense p x nc stripe from every rank's packed windows, rank k's at
 // recv + base[k]; Tb[0..nranks] are the ranks' tile-row boundaries (device arrays)
 void launch_sigma_unpack(const double *recv, int p, int c0, int nc, const int *Tb, const long long *base,

@@ -134,7 +134,7 @@ def local_state(state: dict, s0: int, gl: int) -> dict:
 
 def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hyper(),
                   init_draws=None, iter_draws=None, nranks=1, rank=0, device=0, comm_uid=None,
-                  asm_batch=0, return_info=False, device_ingest=True, device_init=True):
+                  asm_batch=0, return_info=False, device_ingest=True, device_init=True, return_sd=False):
     """Sigmaout = divideconquer(Y,g,k,BURNIN,MCMC,thin,rho)   (divideconquer.m:1).
 
     ``device_ingest`` (default): the zero-column scan and the partition/standardisation
@@ -146,6 +146,11 @@ def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hy
     Multi-GPU: call on every rank with the same arguments plus nranks/rank/device
     and the 128-byte RCCL id (``Sampler.unique_id()`` on rank 0, broadcast by
     the caller).  Every rank returns the full Sigmaout.
+
+    ``return_sd``: also accumulate the second moment of the per-sample covariance on the device
+    (DCFM_FLAG_SIGMA_M2) and return ``(Sigmaout, Sigmasd)`` — or ``(Sigmaout, Sigmasd, info)`` with
+    ``return_info`` — where Sigmasd is the p x p posterior standard deviation of every entry over
+    the saved samples, in Sigmaout's coordinates.
     """
     t0 = time.perf_counter()                                     # dc:29 tic
     if device_ingest:
@@ -167,7 +172,8 @@ def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hy
     gl = g // nranks
     s0 = rank * gl
     smp = Sampler(n, P, g, K, rho, BURNIN, MCMC, thin, hyper=hyper, seed=seed, nranks=nranks,
-                  rank=rank, device=device, inject_draws=iter_draws is not None, asm_batch=asm_batch)
+                  rank=rank, device=device, inject_draws=iter_draws is not None, asm_batch=asm_batch,
+                  sigma_m2=return_sd)
     try:
         if nranks > 1:
             if comm_uid is None:
@@ -185,13 +191,15 @@ def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hy
             smp.set_draws(iter_draws, 1, N)
         smp.run(1, N)                                            # dc:90-197
         Sigmaout = smp.get_sigma()
+        Sigmasd = smp.get_sigma_moment("sd") if return_sd else None
     finally:
         smp.close()
     elapsed = time.perf_counter() - t0                           # dc:200 toc
+    out = (Sigmaout, Sigmasd) if return_sd else (Sigmaout,)
     if return_info:
-        return Sigmaout, {"varind": np.asarray(init.varind), "keep": keep, "n": n, "p": p, "P": P,
-                          "K": K, "N": N, "seconds": elapsed}
-    return Sigmaout
+        out += ({"varind": np.asarray(init.varind), "keep": keep, "n": n, "p": p, "P": P,
+                 "K": K, "N": N, "seconds": elapsed},)
+    return out if len(out) > 1 else out[0]
 
 
 def truth_factors(Lam0, sig2, Y, keep, varind):
@@ -219,7 +227,9 @@ def unpermute_sigma(S, keep, varind, p_orig, sd=None, fill=0.0):
     columns get ``fill``.  With ``sd`` (the sample standard deviations of the kept
     columns in Sigmaout's order, dc:57) the standardisation is undone: S_ab sd_a sd_b.
     The reference returns the permuted, standardised matrix and leaves this to the
-    caller."""
+    caller.  The posterior standard deviation Sigmasd of
+    ``divideconquer(..., return_sd=True)`` goes through the same call: a standard deviation
+    scales like the entry itself, sd(S_ab sd_a sd_b) = sd(S_ab) sd_a sd_b."""
     S = np.asarray(S, dtype=np.float64)
     cols = output_columns(keep, varind)
     if sd is not None:

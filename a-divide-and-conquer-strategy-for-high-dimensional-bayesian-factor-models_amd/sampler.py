@@ -40,7 +40,7 @@ class Sampler:
     """One rank's handle: shards [rank*g_local, (rank+1)*g_local) of a chain."""
 
     def __init__(self, n, P, g, K, rho, burnin, mcmc, thin, *, hyper: Hyper = Hyper(), seed=0,
-                 nranks=1, rank=0, device=0, inject_draws=False, asm_batch=0, flags=0):
+                 nranks=1, rank=0, device=0, inject_draws=False, asm_batch=0, flags=0, sigma_m2=False):
         self.lib = _abi.load_library()
         cfg = _abi.DcfmConfig()
         cfg.n, cfg.P, cfg.g, cfg.K = int(n), int(P), int(g), int(K)
@@ -50,7 +50,8 @@ class Sampler:
         cfg.ad1, cfg.bd1, cfg.ad2, cfg.bd2 = hyper.ad1, hyper.bd1, hyper.ad2, hyper.bd2
         cfg.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         cfg.nranks, cfg.rank, cfg.device = int(nranks), int(rank), int(device)
-        cfg.flags = (_abi.DCFM_FLAG_INJECT_DRAWS if inject_draws else 0) | int(flags)
+        cfg.flags = ((_abi.DCFM_FLAG_INJECT_DRAWS if inject_draws else 0) |
+                     (_abi.DCFM_FLAG_SIGMA_M2 if sigma_m2 else 0) | int(flags))
         cfg.asm_batch = int(asm_batch)
         self.cfg = cfg
         h = C.c_void_p()
@@ -205,6 +206,39 @@ class Sampler:
             return None
         S = np.zeros((p, int(ncols)), dtype=np.float64, order="F")
         self._check(self.lib.dcfm_get_sigma_cols(self.h, int(col0), int(ncols), _ptr(S)))
+        return S
+
+    @staticmethod
+    def _moment(which) -> int:
+        if isinstance(which, str):
+            if which not in _abi.SIGMA_MOMENTS:
+                raise ValueError(f"which must be one of {sorted(_abi.SIGMA_MOMENTS)}, got {which!r}")
+            return _abi.SIGMA_MOMENTS[which]
+        return int(which)
+
+    def get_sigma_moment(self, which):
+        """A posterior moment of Sigma's entries (p x p, Fortran order): ``"mean"`` = get_sigma(),
+        ``"m2"`` the element-wise second moment of the per-sample Sigma (1/effsamp scaling, as the
+        mean), ``"sd"`` the posterior standard deviation over the samples saved so far (population
+        form).  ``"m2"`` / ``"sd"`` need ``sigma_m2=True``.  Collective like get_sigma()."""
+        w = self._moment(which)
+        p = self.P * self.g
+        if self.rank != 0:
+            self._check(self.lib.dcfm_get_sigma_moment(self.h, w, None))
+            return None
+        S = np.zeros((p, p), dtype=np.float64, order="F")
+        self._check(self.lib.dcfm_get_sigma_moment(self.h, w, _ptr(S)))
+        return S
+
+    def get_sigma_moment_cols(self, which, col0: int, ncols: int):
+        """Columns [col0, col0+ncols) of get_sigma_moment(which), p x ncols (as get_sigma_cols)."""
+        w = self._moment(which)
+        p = self.P * self.g
+        if self.rank != 0:
+            self._check(self.lib.dcfm_get_sigma_moment_cols(self.h, w, int(col0), int(ncols), None))
+            return None
+        S = np.zeros((p, int(ncols)), dtype=np.float64, order="F")
+        self._check(self.lib.dcfm_get_sigma_moment_cols(self.h, w, int(col0), int(ncols), _ptr(S)))
         return S
 
     def sigma_block(self) -> dict:

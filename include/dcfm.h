@@ -65,6 +65,11 @@ extern "C" {
                                         path's own residual fallback (K <= 32: resid_rows8 in
                                         the loading-row kernel; K > 32: every tile through
                                         k_resid_flagged) for every row (tests)            */
+#define DCFM_FLAG_SIGMA_M2     0x80u  /* also accumulate the element-wise second moment of the
+                                        per-sample Sigma (a second buffer the size of this rank's
+                                        Sigmaout block, one more assembly kernel per flush), for
+                                        dcfm_get_sigma_moment's M2 and SD; off: nothing is
+                                        allocated or launched                              */
 
 typedef struct dcfm_handle dcfm_handle;
 
@@ -193,9 +198,27 @@ int  dcfm_get_sigma_cols(dcfm_handle *h, int64_t col0, int64_t ncols, double *ou
 /* This rank's block of Sigmaout (the build's output sharding; the reference holds
  * the whole p x p, dc:42): out[0], out[1] = the rows [row0, row1) whose lower
  * triangle it accumulates (contiguous 128-row tiles, balanced by tile count over
- * the ranks), out[2] = its device bytes for Sigmaout (~p^2 / (2 nranks) * 8). */
+ * the ranks), out[2] = its device bytes for Sigmaout (~p^2 / (2 nranks) * 8; twice that
+ * with DCFM_FLAG_SIGMA_M2: the second moment beside the mean). */
 int  dcfm_sigma_block(const dcfm_handle *h, int64_t out[3]);
 int64_t dcfm_saved_samples(const dcfm_handle *h);
+/* Posterior moments of Sigma's entries.  With Sigma(s) the matrix dc:182-192 builds from saved
+ * sample s (Sigma(s)_ab = c_ab Lambda(s)_a . Lambda(s)_b + [a == b] omega(s)_a, c_ab = 1 inside a
+ * shard, rho across), `which` selects
+ *   DCFM_SIGMA_MEAN  Sigmaout = (1/effsamp) sum_s Sigma(s): exactly dcfm_get_sigma_cols;
+ *   DCFM_SIGMA_M2    M2 = (1/effsamp) sum_s Sigma(s).^2, the same effsamp = mcmc/thin scaling
+ *                    (quirk Q8) as the mean;
+ *   DCFM_SIGMA_SD    sqrt(max(0, r M2 - (r Sigmaout).^2)), r = effsamp / dcfm_saved_samples(h):
+ *                    the posterior standard deviation (population form, 1/S) over the samples
+ *                    saved so far, whatever effsamp is; formed on the device from both buffers.
+ * M2 and SD need DCFM_FLAG_SIGMA_M2 (else DCFM_ERR_INVALID); SD with no saved sample is
+ * DCFM_ERR_INVALID.  M2 - mean^2 cancels: an entry keeps about eps M2 / var relative accuracy.
+ * Layout, striping and collective semantics as dcfm_get_sigma_cols / dcfm_get_sigma. */
+#define DCFM_SIGMA_MEAN 0
+#define DCFM_SIGMA_M2   1
+#define DCFM_SIGMA_SD   2
+int  dcfm_get_sigma_moment_cols(dcfm_handle *h, int32_t which, int64_t col0, int64_t ncols, double *out);
+int  dcfm_get_sigma_moment(dcfm_handle *h, int32_t which, double *out);
 /* Error of Sigmaout against a truth Sigma0 = U U' + diag(s) given in the same permuted,
  * standardised coordinates (U: p x r column-major, r <= 32; s: p), computed on the
  * device (Sigmaout never leaves HBM; c5: 80 GB).  out[0] = ||Sigmaout - Sigma0||_F,

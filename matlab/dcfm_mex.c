@@ -6,7 +6,7 @@
  * a mock of the mx / mex API and drives it, argument checking on the CPU and a whole chain
  * on the GPU).  Commands:
  *   h = dcfm_mex('create', cfg)           cfg fields n P g K rho burnin mcmc thin as bs df ad1
- *                                         bd1 ad2 bd2 seed device inject asm_batch
+ *                                         bd1 ad2 bd2 seed device inject asm_batch sigma_m2
  *   dcfm_mex('set_data', h, Yd)           Yd n x P x g (dc:49-59 done by the caller)
  *   dcfm_mex('set_data_raw', h, Y0, cols) raw n x p0 data + int64 0-based columns (dc:48-59 on GPU)
  *   dcfm_mex('set_state', h, Lambda, ps, omega, psijh, Plam, X, Z, delta, tauh)
@@ -16,7 +16,11 @@
  *   dcfm_mex('run', h, first, count)      dc:90-197
  *   [Lambda, ps, omega, psijh, Plam, X, Z, eta, delta, tauh] = dcfm_mex('get_state', h)
  *   S = dcfm_mex('get_sigma', h)          Sigmaout (dc:194-195), p x p from the handle
- *   e = dcfm_mex('error', h, U, s, iters) [||S-S0||_F, ||S0||_F, ||S-S0||_2] vs S0 = UU' + diag(s)
+ *   M = dcfm_mex('sigma_moment', h, which[, col0, ncols])   which = 'mean' | 'm2' | 'sd': posterior
+ *                                         mean, second moment or standard deviation of Sigma's
+ *                                         entries ('m2', 'sd' need cfg.sigma_m2 = 1), p x p or
+ *                                         the columns col0 .. col0+ncols-1 (0-based), p x ncols
+ *   e = dcfm_mex('error', h, U, s, iters)[||S-S0||_F, ||S0||_F, ||S-S0||_2] vs S0 = UU' + diag(s)
  *   dcfm_mex('set_trace', h, cap); T = dcfm_mex('get_trace', h)     chain trace (count x 4)
  *   dcfm_mex('destroy', h)
  * Every array argument is checked (class double, real, element count from the handle's
@@ -94,6 +98,7 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         c.ad1 = fld(s, "ad1", 2); c.bd1 = fld(s, "bd1", 1); c.ad2 = fld(s, "ad2", 2); c.bd2 = fld(s, "bd2", 1);
         c.seed = (uint64_t)fld(s, "seed", 0); c.nranks = 1; c.device = (int32_t)fld(s, "device", 0);
         c.flags = fld(s, "inject", 0) != 0 ? DCFM_FLAG_INJECT_DRAWS : 0u;
+        if (fld(s, "sigma_m2", 0) != 0) c.flags |= DCFM_FLAG_SIGMA_M2;
         c.asm_batch = (int32_t)fld(s, "asm_batch", 0);
         int i = 0;
         while (i < NSLOT && S[i].h) ++i;
@@ -231,6 +236,32 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
                               (long long)p);
         plhs[0] = mxCreateDoubleMatrix((mwSize)p, (mwSize)p, mxREAL);
         ck(t->h, dcfm_get_sigma(t->h, mxGetDoubles(plhs[0])));
+    } else if (!strcmp(cmd, "sigma_moment")) {       /* M = dcfm_mex('sigma_moment', h, which[, col0, ncols]) */
+        if (nrhs != 3 && nrhs != 5)
+            mexErrMsgIdAndTxt("dcfm:nargs", "'%s' takes 2 or 4 arguments, got %d", cmd, nrhs - 1);
+        /* the arguments that need no handle first: a malformed call never reaches the library */
+        char wn[8];
+        int32_t which = -1;
+        if (mxIsChar(prhs[2]) && mxGetString(prhs[2], wn, sizeof wn) == 0) {
+            if (!strcmp(wn, "mean")) which = DCFM_SIGMA_MEAN;
+            else if (!strcmp(wn, "m2")) which = DCFM_SIGMA_M2;
+            else if (!strcmp(wn, "sd")) which = DCFM_SIGMA_SD;
+        }
+        if (which < 0) mexErrMsgIdAndTxt("dcfm:arg", "which must be 'mean', 'm2' or 'sd'");
+        double c0 = 0, nc = -1;                      /* 0-based first column and count; default: all */
+        if (nrhs == 5) {
+            c0 = scalar(prhs[3], "col0");
+            nc = scalar(prhs[4], "ncols");
+            if (c0 < 0 || nc < 0 || c0 != (double)(int64_t)c0 || nc != (double)(int64_t)nc)
+                mexErrMsgIdAndTxt("dcfm:arg", "col0 and ncols must be non-negative integers");
+        }
+        slot *t = get(prhs[1]);
+        const int64_t p = t->P * t->g;               /* the size the library writes */
+        if (nc < 0) nc = (double)p;
+        if (c0 + nc > (double)p)
+            mexErrMsgIdAndTxt("dcfm:arg", "columns [%g, %g) outside 0..p = %lld", c0, c0 + nc, (long long)p);
+        plhs[0] = mxCreateDoubleMatrix((mwSize)p, (mwSize)nc, mxREAL);
+        ck(t->h, dcfm_get_sigma_moment_cols(t->h, which, (int64_t)c0, (int64_t)nc, mxGetDoubles(plhs[0])));
     } else if (!strcmp(cmd, "destroy")) {
         nargs(nrhs, 2, cmd);
         slot *t = get(prhs[1]);

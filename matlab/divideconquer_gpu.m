@@ -1,4 +1,4 @@
-function Sigmaout = divideconquer_gpu(Y, g, k, BURNIN, MCMC, thin, rho, seed)
+function [Sigmaout, Sigmasd] = divideconquer_gpu(Y, g, k, BURNIN, MCMC, thin, rho, seed)
 % DIVIDECONQUER_GPU  Sigmaout = divideconquer_gpu(Y,g,k,BURNIN,MCMC,thin,rho[,seed])
 % Same arguments and output as divideconquer.m:1 (posterior-mean covariance in the
 % permuted, standardised coordinates, quirk Q7), with the driver (dc:29-87) and the loop
@@ -8,6 +8,9 @@ function Sigmaout = divideconquer_gpu(Y, g, k, BURNIN, MCMC, thin, rho, seed)
 %   dc:68-87  initial state on the GPU from the library's Philox stream (init_state);
 %   dc:90-197 the Gibbs sweep and covariance assembly (run), read back (get_sigma).
 % varind = randperm(p) (dc:50) is drawn from MATLAB's stream as in the reference.
+% [Sigmaout, Sigmasd] = divideconquer_gpu(...) also returns the posterior standard deviation
+% of every entry of Sigma over the saved samples (same coordinates): the second moment of the
+% per-sample covariance is accumulated on the GPU beside the mean (cfg.sigma_m2).
 if nargin < 8, seed = 0; end
 [n, p0] = size(Y);
 keepcols = find(arrayfun(@(j) nnz(Y(:, j)), 1:p0) > 0);   % dc:31-38
@@ -19,11 +22,12 @@ end
 varind = randperm(p);                                      % dc:50
 cfg = struct('n', n, 'P', P, 'g', g, 'K', K, 'rho', rho, 'burnin', BURNIN, 'mcmc', MCMC, ...
              'thin', thin, 'as', 1, 'bs', 0.3, 'df', 3, 'ad1', 2, 'bd1', 1, 'ad2', 2, 'bd2', 1, ...
-             'seed', seed);
+             'seed', seed, 'sigma_m2', double(nargout > 1));
 h = dcfm_mex('create', cfg);
 cleanup = onCleanup(@() dcfm_mex('destroy', h));
 dcfm_mex('set_data_raw', h, Y, int64(keepcols(varind) - 1));  % dc:48-59 on the device
 dcfm_mex('init_state', h);                                     % dc:68-87 on the device
 dcfm_mex('run', h, 1, BURNIN + MCMC);                          % dc:90-197
 Sigmaout = dcfm_mex('get_sigma', h, p);
+if nargout > 1, Sigmasd = dcfm_mex('sigma_moment', h, 'sd'); end
 end

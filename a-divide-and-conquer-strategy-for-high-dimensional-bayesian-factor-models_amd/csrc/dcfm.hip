@@ -3,6 +3,7 @@
 // in its two layouts.  Collectives: comm.hip; data and state I/O: state_io.hip; the Sigma
 // read-out: sigma_out.hip.
 #include "handle.h"
+#include "resid.h"   // KAPPA_IDENTITY_MAX
 
 static int dalloc(dcfm_handle *h, double **p, size_t n) {
     void *q = nullptr;
@@ -441,15 +442,14 @@ static void loading_rows(dcfm_handle *h, const DrawsDev &dr, int64_t it, bool la
     const Dims &d = h->d;
     const Bufs &b = h->b;
     hipStream_t s = h->stream;
+    // exact residual: k_resid redoes every row below (the guard need not fire); GUARD_ALL: it rejects every row
+    const bool exact = h->cfg.flags & DCFM_FLAG_EXACT_RESIDUAL;
+    const double kappa_max = exact ? HUGE_VAL : (h->cfg.flags & DCFM_FLAG_GUARD_ALL) ? 0.0 : KAPPA_IDENTITY_MAX;
     {
         KTimer t(h, DCFM_K_LAMBDA, s);
-        // exact residual: k_resid redoes every row below (the guard need not fire)
-        const bool exact = h->cfg.flags & DCFM_FLAG_EXACT_RESIDUAL;
-        const double kmax = (h->cfg.flags & DCFM_FLAG_GUARD_ALL) ? 0.0 : KAPPA_IDENTITY_MAX;
-        launch_lambda(d, b, dr, it, delta_tau(h).tau_in, h->plam_valid ? b.Plam : nullptr, s, lamgen,
-                      exact ? HUGE_VAL : kmax);
+        launch_lambda(d, b, dr, it, delta_tau(h).tau_in, h->plam_valid ? b.Plam : nullptr, s, lamgen, kappa_max);
     }
-    if (h->cfg.flags & DCFM_FLAG_EXACT_RESIDUAL) {   // dc:169's residual for every loading row
+    if (exact) {                                      // dc:169's residual for every loading row
         KTimer t(h, DCFM_K_RESID, s);
         launch_resid(d, b, dr, it, s, lamgen);
     } else if (d.kp != KP) {                          // K > 32: the tiles k_lambda_w's guard flagged

@@ -129,6 +129,18 @@ struct Bufs {
     int T0, T1;                        // owned tile rows of Sigma (block-sharded, see above)
 };
 
+// This iteration's loading-row variates for this rank's shards.  gen: the buffer k_wcol's extra blocks
+// filled (the generated fused chain, K <= 32); else the [T][g][P][K] / [T][g][P] draw buffers dr
+// (injected draws, k_draws batches) at iter and the rank's first shard
+inline LamDraws lam_draws_at(const Dims &d, const Bufs &b, const DrawsDev &dr, int64_t iter, bool gen) {
+    if (gen) {
+        const LamGen g = lam_gen_plan(d, b.ldraw);
+        return {g.NL, g.Gpsi, g.Gps};
+    }
+    const size_t row0 = ((size_t)(iter - dr.first_iter) * d.g + d.shard0) * d.P;
+    return {dr.NL + row0 * d.K, dr.Gpsi + row0 * d.K, dr.Gps + row0};
+}
+
 // k_wcol shard sum of A
 constexpr int XSUM_BLOCKS = 8;
 constexpr int TRACE_SLICES = 16;       // k_trace_part blocks per local shard (slices of its loading rows)
@@ -199,17 +211,11 @@ void launch_xdraw(const Dims &d, const Bufs &b, const DrawsDev &dr, int64_t iter
 void launch_cpass(const Dims &d, const Bufs &b, hipStream_t s, const DrawsDev &dr = DrawsDev{},
                   const double *delta_in = nullptr, const double *tau_in = nullptr, double *delta_out = nullptr,
                   double *tau_out = nullptr, int64_t delta_iter = 0);
-// gen: K <= 32 reads the variates k_wcol generated into b.ldraw (the generated fused chain)
-// instead of the draw buffers dr (injected draws, k_draws batches).
-// K <= 32: a wave whose SS identity may be off by more than ~kappa_max eps for one of its rows (lambda.h
-// guard) takes its rows' ps, omega from dc:169's direct residual instead (resid_rows8, same launch)
-#ifndef DCFM_KAPPA_MAX
-#define DCFM_KAPPA_MAX 1e3
-#endif
-constexpr double KAPPA_IDENTITY_MAX = DCFM_KAPPA_MAX;
+// gen: lam_draws_at.  kappa_max: a row whose SS identity may be off by more than ~kappa_max eps (the
+// guard, resid.h) takes ps, omega from dc:169's direct residual instead: K <= 32 its wave's 8 rows in
+// the same launch, K > 32 its 32-row tile in launch_resid_flagged
 void launch_lambda(const Dims &d, const Bufs &b, const DrawsDev &dr, int64_t iter,
-                   const double *tau_cur, const double *plam_src, hipStream_t s, bool gen = false,
-                   double kappa_max = KAPPA_IDENTITY_MAX);
+                   const double *tau_cur, const double *plam_src, hipStream_t s, bool gen, double kappa_max);
 void launch_colsum(const Dims &d, const Bufs &b, hipStream_t s);
 // resid.hip (DCFM_FLAG_EXACT_RESIDUAL): ps, omega from the direct residual Yd - eta Lambda' (dc:169-171)
 // for every loading row, after the loading-row kernel, with its ps variates (gen: b.ldraw, else dr)

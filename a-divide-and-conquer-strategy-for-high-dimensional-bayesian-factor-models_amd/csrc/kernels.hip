@@ -4,7 +4,7 @@
 // kernels of the sweep, k_wcol's role dispatch and the launchers; the role bodies are in the
 // stage headers: zx_ops.h (K x K operators of the Z / X draws), ypass.h (the two Y passes),
 // zdraw.h (Z draw), draws.h (variates), delta.h (column sums, delta / tau chain), lambda.h
-// (loading rows), handoff.h (hand-off between blocks of one launch).  The covariance assembly
+// (loading rows; its dc:169-171 is resid.h), handoff.h (hand-off between blocks of one launch).  The covariance assembly
 // is assemble.hip, the K > 32 kernels kernels_wide.hip.
 //
 // Kernel map (per iteration, in order)                         reference lines
@@ -687,16 +687,7 @@ void launch_cpass(const Dims &d, const Bufs &b, hipStream_t s, const DrawsDev &d
 void launch_lambda(const Dims &d, const Bufs &b, const DrawsDev &dr, int64_t iter,
                    const double *tau_cur, const double *plam_src, hipStream_t s, bool gen, double kappa_max) {
     if (d.kp != KP) return wide::launch_lambda(d, b, dr, iter, tau_cur, plam_src, s, kappa_max);
-    LamDraws ld;
-    if (gen) {   // this iteration's variates, drawn by k_wcol's LAMGEN blocks (lam_draws)
-        const LamGen g = lam_gen_plan(d, b.ldraw);
-        ld.NL = g.NL; ld.Gpsi = g.Gpsi; ld.Gps = g.Gps;
-    } else {     // [T][g][P][K] / [T][g][P] draw buffers: this iteration, this rank's first shard
-        const size_t row0 = ((size_t)(iter - dr.first_iter) * d.g + d.shard0) * d.P;
-        ld.NL = dr.NL + row0 * d.K;
-        ld.Gpsi = dr.Gpsi + row0 * d.K;
-        ld.Gps = dr.Gps + row0;
-    }
+    const LamDraws ld = lam_draws_at(d, b, dr, iter, gen);
     const dim3 grid(cdiv(d.P, LAM_ROWS), d.G);
 #define LAUNCH_LAM(KE)                                                                                       \
     hipLaunchKernelGGL(k_lambda<KE>, grid, dim3(64), 0, s, d, b.C, b.E, b.yy, tau_cur, b.Lam, b.psi, plam_src, \

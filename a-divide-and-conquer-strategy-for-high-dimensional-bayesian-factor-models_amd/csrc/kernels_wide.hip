@@ -24,6 +24,7 @@
 #include "linalg.h"
 #include "tile_linalg.h"
 #include "delta.h"
+#include "resid.h"
 
 namespace dcfm {
 namespace wide {
@@ -383,7 +384,8 @@ __global__ __launch_bounds__(64 * xd_waves<KW>()) void k_xdraw(Dims d, const dou
 // before one reduction over the 16 lanes of a tile row.  No workgroup barriers: the row's
 // whole chain is one wave, and the CU's other waves (other rows) fill its latency.  The
 // epilogue forms psi (dc:150), cpart (dc:156) and SS_j = yy_j - 2 x.C_j + x'E x (dc:169 by
-// identity: x'E x = (|w|^2 - sum_r Plam_jr x_r^2) / ps_j since x'Q_j x = |w|^2), ps, omega.
+// identity: x'E x = (|w|^2 - sum_r Plam_jr x_r^2) / ps_j since x'Q_j x = |w|^2), ps, omega and the
+// identity's guard (both resid.h).
 // ============================================================================
 template <int NB>
 __host__ __device__ constexpr int utix(int Kc, int I) { return Kc * NB - Kc * (Kc - 1) / 2 + (I - Kc); }
@@ -614,10 +616,10 @@ __global__ __launch_bounds__(64) void k_lambda_w(
         if (lane + 64 * h >= 16 * NB) vx[lane + 64 * h] = 0.0;
     __syncthreads();
     // ---- epilogue: Lambda_j, psi_j (dc:150), cpart (dc:156), SS_j (dc:169), ps_j, omega_j
-    //      + the guard of the SS identity (as k_lambda's, lambda.h): kappa_j = max(yy_j + (1 + c_j) |w|^2 / ps_j
-    //      + sum_r Plam_jr x_r^2 / ps_j + 2 sum_r |x_r C_jr|,  (sqrt(yy_j) + sum_r |x_r| sqrt(E_rr))^2) / SS_j,
-    //      c_j = max_r Q_rr / L_rr^2; a row beyond kappa_max (or SS_j <= 0) flags its 32-row tile, whose
-    //      ps, omega k_resid_flagged then takes from dc:169's residual
+    //      + the guard of the SS identity (resid.h, ss_identity_reject) from the row's sums mag_j = (1 + c_j)
+    //      |w|^2 / ps_j + sum_r Plam_jr x_r^2 / ps_j + 2 sum_r |x_r C_jr|, c_j = max_r Q_rr / L_rr^2, and
+    //      sabs_j = sum_r |x_r| sqrt(E_rr); a rejected row flags its 32-row tile, whose ps, omega
+    //      k_resid_flagged then takes from dc:169's residual
     double ssr = 0.0, mag = 0.0, ww = 0.0, sab = 0.0, cs = 1.0;
 #pragma unroll
     for (int h = 0; h < NH; ++h) {
@@ -656,14 +658,9 @@ __global__ __launch_bounds__(64) void k_lambda_w(
     cs = fmax(fmax(readlane_d(cs, 0), readlane_d(cs, 16)), fmax(readlane_d(cs, 32), readlane_d(cs, 48)));
     if (lane == 0) {
         const double SS = yyj + ssr;
-        const double psn = (1.0 / (d.bs + 0.5 * SS)) * Gps;      // dc:170
-        ps[(size_t)m * d.PP + j] = psn;
-        omega[(size_t)m * d.PP + j] = 1.0 / psn;                 // dc:171 (Q1)
-        if (rflag) {
-            const double rt = 1.01 * (yyj * __builtin_amdgcn_rsq(yyj) + sab);
-            const double num = fmax(rt * rt, 1.01 * (yyj + mag + (1.0 + cs) * ww / psj));
-            if (!(SS > 0.0 && num <= kappa_max * SS)) rflag[m * (d.PP / 32) + j / 32] = 1;
-        }
+        ps_omega_store(d, SS, Gps, ps, omega, (size_t)m * d.PP + j);
+        if (rflag && ss_identity_reject(yyj, SS, mag + (1.0 + cs) * ww / psj, sab, kappa_max))
+            rflag[m * (d.PP / 32) + j / 32] = 1;
     }
 }
 

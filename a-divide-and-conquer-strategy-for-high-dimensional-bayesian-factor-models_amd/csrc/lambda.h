@@ -1,9 +1,11 @@
 // Loading-row kernel of the narrow (K <= 32) chain and the generator of its variates
-// (divideconquer.m:140-145, 150, 156, 169-171), included by kernels.hip.
+// (divideconquer.m:140-145, 150, 156, 169-171), included by kernels.hip.  dc:169-171 itself (the ps /
+// omega formula, the guard of the SS identity, the direct residual of a wave's rows) is in resid.h.
 #pragma once
 #include "dcfm_internal.h"
 #include "philox.h"
 #include "linalg.h"
+#include "resid.h"
 
 namespace dcfm {
 
@@ -99,7 +101,8 @@ __device__ __forceinline__ void lam_draws(const Dims &d, const LamGen &lg, int64
 //   * Back solve L' x = w from the bottom, the sums over the group's rows as 8-lane DPP sums.
 //   * psi_j (dc:150, tau of the previous iteration), SS_j = yy_j - 2 x.C_j + x'E x with
 //     x'E x = (|w|^2 - sum_r Plam_jr x_r^2) / ps_j and ps_j x.C_j = w.v (no third Y pass, no
-//     second read of E or C), ps_j and omega_j (dc:169-171), psi o Lambda^2 -> cpart (dc:156).
+//     second read of E or C), ps_j and omega_j (dc:169-171; where the guard rejects the identity for a
+//     row, the wave's 8 rows by the direct residual: resid.h), psi o Lambda^2 -> cpart (dc:156).
 // Plam_j = psi_j o tau' (dc:176) is formed from the previous iteration's psi and tau unless
 // plam_src is given (first iteration after dcfm_set_state).  The row's variates (dc:142, 150,
 // 170) come from a draw buffer: the generated chain's k_wcol draws them (lam_draws),
@@ -121,53 +124,6 @@ __device__ __forceinline__ double rowsum8(double v) {
     return v;
 }
 
-constexpr int LAM_ROWS = 8;   // loading rows per wave
-
-// dc:169-171 as written for the wave's 8 loading rows j0 .. j0+7 (the guard below, or the exact
-// mode): Ytil = Yd - eta Lambda' as fp64 MFMA v_mfma_f64_16x16x4 over 16-row chunks of i, the Y
-// values as the accumulator input and -eta as the A operand (the subtraction of dc:169 inside the
-// accumulation); B = the rows' Lambda from the LDS image Lm (columns 8..15 of the tile zero); lane
-// (c, q) holds Ytil for rows i0 + q + 4v of loading row j0 + c and squares them into its sum, the
-// 4 lanes of a row then summed in a fixed order.  ps_j, omega_j with the row's gamma variate Gps.
-__device__ __forceinline__ void resid_rows8(const Dims &d, const double *__restrict__ Y,
-                                            const double *__restrict__ X, const double *__restrict__ Z,
-                                            const double (*Lm)[KP + 1], double Gps_c, int m, int j0, int lane,
-                                            double *__restrict__ ps, double *__restrict__ omega) {
-    constexpr int NT = KP / 8;
-    const int c = lane & 15, q = lane >> 4;
-    const bool col = c < LAM_ROWS && j0 + c < d.P;
-    d2 lb[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        lb[t].x = col ? Lm[c][8 * t + 2 * q] : 0.0;
-        lb[t].y = col ? Lm[c][8 * t + 2 * q + 1] : 0.0;
-    }
-    const double *Ym = Y + (size_t)m * d.NP * d.PP + (col ? j0 + c : 0);
-    const double *Zm = Z + (size_t)m * d.NP * KP + 2 * q;
-    double ss = 0.0;
-    for (int i0 = 0; i0 < d.NP; i0 += 16) {
-        d4 acc;
-#pragma unroll
-        for (int v = 0; v < 4; ++v) acc[v] = col ? Ym[(size_t)(i0 + q + 4 * v) * d.PP] : 0.0;
-        const double *xr = X + (size_t)(i0 + c) * KP + 2 * q, *zr = Zm + (size_t)(i0 + c) * KP;
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-            const d2 xa = *reinterpret_cast<const d2 *>(xr + 8 * t);
-            const d2 za = *reinterpret_cast<const d2 *>(zr + 8 * t);
-            acc = mfma16x16x4_na(eta_of(d.sr, d.s1r, xa.x, za.x), lb[t].x, acc);
-            acc = mfma16x16x4_na(eta_of(d.sr, d.s1r, xa.y, za.y), lb[t].y, acc);
-        }
-#pragma unroll
-        for (int v = 0; v < 4; ++v) ss = (i0 + q + 4 * v < d.n) ? fma(acc[v], acc[v], ss) : ss;   // data rows only
-    }
-    ss += xor16_d(ss);   // (q0 + q1) + (q2 + q3)
-    ss += xor32_d(ss);
-    if (q == 0 && col) {
-        const double psn = (1.0 / (d.bs + 0.5 * ss)) * Gps_c;   // dc:170
-        ps[(uint32_t)(m * d.PP + j0 + c)] = psn;
-        omega[(uint32_t)(m * d.PP + j0 + c)] = 1.0 / psn;        // dc:171 (Q1)
-    }
-}
 constexpr int LAM_PIPE = 4;   // image columns read ahead of their trailing-update FMAs
 __host__ __device__ constexpr int lam_ncol(int KE, int b) { return 8 * b + 8 < KE ? 8 * b + 8 : KE; }
 
@@ -470,16 +426,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_
     double contrib = (ww - px - 2.0 * wv) * ipsj;
     contrib = valid ? contrib : 0.0;
     contrib = rowsum8(contrib);
-    // ---- guard: the identity's rounding error is ~ kappa_j eps, kappa_j = (the magnitudes it sums) / SS_j.
-    //      Two bounds on those magnitudes, the larger taken:
-    //      * as computed: yy_j + (|w|^2 + sum_r Plam_jr x_r^2 + 2 sum_r |w_r v_r|) / ps_j, with |w|^2 weighted
-    //        by 1 + c_j, c_j = max_k Q_kk / L_kk^2 (>= 1, scale-invariant): w = L'x holds only to the back
-    //        solve's backward error, which grows with the elimination's loss of the diagonal;
-    //      * a priori: yy_j + 2 sum_k |x_k C_jk| + |x|'|E||x| <= (sqrt(yy_j) + s_j)^2, s_j = sum_k |x_k|
-    //        sqrt(E_kk) (|C_jk| <= sqrt(E_kk yy_j) and |E_kl| <= sqrt(E_kk E_ll), E a Gram matrix).
-    //      Beyond kappa_max (or SS_j <= 0) the wave's 8 rows take dc:169's residual instead (resid_rows8).
-    //      Square roots as v * rsq(v) from the hardware estimate (a bound needs no correct rounding; the
-    //      factor 1.01 covers its error); a zero yy_j gives NaN, read as "take the residual"
+    // ---- guard (resid.h, ss_identity_reject): the row's magnitude sums; one rejected row sends the wave's
+    //      8 rows to dc:169's residual below
     double sabs = 0.0;
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
@@ -492,12 +440,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_
     double mag = valid ? (fma(cs + 1.0, ww, px) + 2.0 * wva) * ipsj : 0.0;
     sabs = rowsum8(sabs);
     mag = rowsum8(mag);
-    bool exact;
-    {
-        const double SS = yyj + contrib, rt = 1.01 * (yyj * __builtin_amdgcn_rsq(yyj) + sabs);
-        const double num = fmax(rt * rt, 1.01 * (yyj + mag));
-        exact = __any(valid && !(SS > 0.0 && num <= kappa_max * SS));
-    }
+    const double SS = yyj + contrib;
+    const bool reject = ss_identity_reject(yyj, SS, mag, sabs, kappa_max);   // in every lane: no branch on valid
+    const bool exact = __any(valid && reject);
     // ---- psi (dc:150, tau of the previous iteration, Q11) and the outputs
     if (valid) {
 #pragma unroll
@@ -518,10 +463,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_
         const double gps_c = ld.Gps[(uint32_t)(m * d.P) + (j0 + cc < d.P && cc < LAM_ROWS ? j0 + cc : 0)];
         resid_rows8(d, Y, X, Z, Lm, gps_c, m, j0, lane, ps, omega);
     } else if (valid && l == 0) {
-        const double SS = yyj + contrib;
-        const double psn = (1.0 / (d.bs + 0.5 * SS)) * Gps;     // dc:170
-        ps[(uint32_t)(m * d.PP + j)] = psn;
-        omega[(uint32_t)(m * d.PP + j)] = 1.0 / psn;            // dc:171 (Q1)
+        ps_omega_store(d, SS, Gps, ps, omega, (uint32_t)(m * d.PP + j));
     }
 }
 

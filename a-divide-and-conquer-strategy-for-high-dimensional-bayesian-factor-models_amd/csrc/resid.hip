@@ -1,24 +1,23 @@
-// Residual-precision update by the reference's own formula for every loading row, as a launch of
-// its own after the loading-row kernel (DCFM_FLAG_EXACT_RESIDUAL), or (K > 32, default mode) for the
-// 32-row tiles whose SS identity k_lambda_w's guard rejected (k_resid_flagged).  The default K <= 32
-// chain runs the same arithmetic per wave inside k_lambda where its guard rejects the identity
-// (lambda.h, resid_rows8).
+// Launches of the residual-precision update by the reference's own formula (resid.h): after the
+// loading-row kernel for every loading row (DCFM_FLAG_EXACT_RESIDUAL: k_resid64 for K <= 32, k_resid<KW>
+// above), or (K > 32, default mode) for the 32-row tiles whose SS identity k_lambda_w's guard rejected
+// (k_resid_flagged).  The default K <= 32 chain runs the same arithmetic per wave inside k_lambda
+// where its guard rejects the identity (resid_rows8).
 //
 // The default chain forms SS_j = sum_i Ytil_ij^2 inside the loading-row kernel by the identity
 // yy_j - 2 lambda_j.C_j + lambda_j E lambda_j' (no Y pass).  That sum cancels when SS_j is
 // small against its terms: its rounding error grows like kappa_j eps with kappa_j = (yy_j +
 // 2 sum_k |lambda_jk C_jk| + |lambda_j| |E| |lambda_j|') / SS_j (measured ~1e6 at the second
 // iteration of config c2, where the X excursions make E large: 1.3e-10 relative in SS).  The
-// direct residual's error grows like sqrt(kappa_j) eps.  k_resid overwrites ps and omega from the
-// direct residual (resid.h): a pass over the tile's Y columns, the reference's own third product.
-//
-// k_resid<KW>: block = (32-column tile of shard m's loading rows, shard m), resid_tile's 4 waves.
+// direct residual's error grows like sqrt(kappa_j) eps.  These kernels overwrite ps and omega from the
+// direct residual: a pass over the tile's Y columns, the reference's own third product.
 #include <algorithm>
 
 #include "resid.h"
 
 namespace dcfm {
 
+// k_resid<KW>: block = (32-column tile of shard m's loading rows, shard m), resid_tile's 4 waves
 template <int KW>
 __global__ __launch_bounds__(256) void k_resid(Dims d, const double *__restrict__ Y, const double *__restrict__ X,
                                                const double *__restrict__ Z, const double *__restrict__ Lam,
@@ -29,21 +28,12 @@ __global__ __launch_bounds__(256) void k_resid(Dims d, const double *__restrict_
 }
 
 // k_resid64 (K <= 32, DCFM_FLAG_EXACT_RESIDUAL): block = (64 loading rows j0 .. j0+63 of shard m) x
-// RW waves; wave w takes the 16-row chunks ch = w, w + RW, ... of i.  Per chunk a wave forms Ytil
-// for 16 rows x 64 columns as four independent fp64 MFMA chains (column tiles h = 0..3, the Y
-// values the accumulator input, -eta the shared A operand: the subtraction of dc:169 inside the
-// accumulation), with the next chunk's Y, X and Z loads in flight behind them; lane (c, q) squares
-// Ytil for rows i0 + q + 4v of columns j0 + 16h + c into its sums.  The 4 lanes of a column, then
-// the RW waves, are summed in a fixed order.  (resid_tile's 32-column tiles ran two chains per
-// wave: 65 us at c3 against this kernel's four.)
-#ifndef DCFM_RESID_RW
-#define DCFM_RESID_RW 4
-#endif
-#ifndef DCFM_RESID_WPE
-#define DCFM_RESID_WPE 2
-#endif
-constexpr int RW = DCFM_RESID_RW;
-__global__ __launch_bounds__(64 * RW) __attribute__((amdgpu_waves_per_eu(DCFM_RESID_WPE))) void k_resid64(
+// RW waves; wave w takes the 16-row chunks ch = w, w + RW, ... of i.  Per chunk a wave runs resid_chunk
+// on four column tiles (four independent MFMA chains sharing the A operand), with the next chunk's Y, X
+// and Z loads in flight behind them.  The 4 lanes of a column, then the RW waves, are summed in a fixed
+// order.  (resid_tile's 32-column tiles ran two chains per wave: 65 us at c3 against this kernel's four.)
+constexpr int RW = 4;   // the sum over waves below is written for 4
+__global__ __launch_bounds__(64 * RW) __attribute__((amdgpu_waves_per_eu(2))) void k_resid64(
     Dims d, const double *__restrict__ Y, const double *__restrict__ X, const double *__restrict__ Z,
     const double *__restrict__ Lam, const double *__restrict__ Gps, double *__restrict__ ps,
     double *__restrict__ omega) {
@@ -64,7 +54,7 @@ __global__ __launch_bounds__(64 * RW) __attribute__((amdgpu_waves_per_eu(DCFM_RE
 #pragma unroll
     for (int hp = 0; hp < 2; ++hp) ho[hp] = (j0 + 32 * hp < d.PP) ? 32 * hp : 0;   // invalid: re-read pair 0
     __syncthreads();
-    d2 lb[4][4];   // B operands Lambda[j0 + 16h + c][8t + 2q .. +1], register-resident for the block
+    d2 lb[4][4];   // B operands Lambda[j0 + jc(h)][8t + 2q .. +1], register-resident for the block
 #pragma unroll
     for (int h = 0; h < 4; ++h)
 #pragma unroll
@@ -78,9 +68,9 @@ __global__ __launch_bounds__(64 * RW) __attribute__((amdgpu_waves_per_eu(DCFM_RE
     double ss[4] = {0.0, 0.0, 0.0, 0.0};
     // Y of the next chunk is loaded a chunk ahead (two register sets); X and Z of the next chunk as soon
     // as this chunk's eta is formed (their registers are free then), so both are in flight behind the MFMAs
-    double yA[4][4], yB[4][4];
+    d4 yA[4], yB[4];   // an invalid tile's values (pair 0 again) only reach sums that nothing stores
     d2 xv[4], zv[4];
-    auto load_y = [&](int ch, double (&y)[4][4]) {
+    auto load_y = [&](int ch, d4 (&y)[4]) {
         const int i0 = 16 * ch;
 #pragma unroll
         for (int v = 0; v < 4; ++v) {   // unconditional loads: an invalid column pair (j >= PP) re-reads pair 0
@@ -108,58 +98,30 @@ __global__ __launch_bounds__(64 * RW) __attribute__((amdgpu_waves_per_eu(DCFM_RE
     }
 #pragma unroll 1
     for (int ch = w; ch < nch; ch += RW) {
-        double e[4][2];
+        d2 eta[4];
 #pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            e[t][0] = -eta_of(d.sr, d.s1r, xv[t].x, zv[t].x);
-            e[t][1] = -eta_of(d.sr, d.s1r, xv[t].y, zv[t].y);
-        }
+        for (int t = 0; t < 4; ++t) eta[t] = eta_pair(d, xv[t], zv[t]);
         __builtin_amdgcn_sched_barrier(0);
-        const bool more = ch + RW < nch;
-        if (more) {
+        if (ch + RW < nch) {
             load_xz(ch + RW);
             load_y(ch + RW, yB);
         }
         __builtin_amdgcn_sched_barrier(0);
-        d4 acc[4];
+        resid_chunk(yA, [&](int t) { return eta[t]; }, lb, 16 * ch + q, d.n, ss);
 #pragma unroll
-        for (int h = 0; h < 4; ++h) acc[h] = d4{yA[h][0], yA[h][1], yA[h][2], yA[h][3]};   // invalid tiles: unused sums
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-#pragma unroll
-            for (int h = 0; h < 4; ++h) acc[h] = mfma16x16x4(e[t][0], lb[h][t].x, acc[h]);
-#pragma unroll
-            for (int h = 0; h < 4; ++h) acc[h] = mfma16x16x4(e[t][1], lb[h][t].y, acc[h]);
-        }
-        const int i0 = 16 * ch;
-#pragma unroll
-        for (int h = 0; h < 4; ++h)
-#pragma unroll
-            for (int v = 0; v < 4; ++v) ss[h] = (i0 + q + 4 * v < d.n) ? fma(acc[h][v], acc[h][v], ss[h]) : ss[h];
-#pragma unroll
-        for (int h = 0; h < 4; ++h)
-#pragma unroll
-            for (int v = 0; v < 4; ++v) yA[h][v] = yB[h][v];
+        for (int h = 0; h < 4; ++h) yA[h] = yB[h];
     }
+    resid_lanesum(ss);
 #pragma unroll
-    for (int h = 0; h < 4; ++h) {   // the column's 4 lane rows: (q0 + q1) + (q2 + q3)
-        ss[h] += xor16_d(ss[h]);
-        ss[h] += xor32_d(ss[h]);
+    for (int h = 0; h < 4; ++h)
         if (q == 0) red[w][jc(h)] = ss[h];
-    }
     __syncthreads();
     if (threadIdx.x < 64) {
         const int t = threadIdx.x, j = j0 + t;
-        double SS = (red[0][t] + red[1][t]) + (red[2][t] + red[3][t]);
-        if constexpr (RW == 8) SS += (red[4][t] + red[5][t]) + (red[6][t] + red[7][t]);
-        if (j < d.P) {
-            const double psn = (1.0 / (d.bs + 0.5 * SS)) * Gps[(size_t)m * d.P + j];   // dc:170
-            ps[(size_t)m * d.PP + j] = psn;
-            omega[(size_t)m * d.PP + j] = 1.0 / psn;                                  // dc:171 (Q1)
-        }
+        const double SS = (red[0][t] + red[1][t]) + (red[2][t] + red[3][t]);
+        if (j < d.P) ps_omega_store(d, SS, Gps[(size_t)m * d.P + j], ps, omega, (size_t)m * d.PP + j);
     }
 }
-static_assert(RW == 4 || RW == 8, "k_resid64's wave tree is written for 4 or 8 waves");
 
 // K > 32 default mode: only the 32-row tiles whose guard k_lambda_w tripped (b.rflag); a flag is
 // read by every thread before resid_tile's barrier and cleared by thread 0 after it
@@ -180,7 +142,7 @@ __global__ __launch_bounds__(256) void k_resid_flagged(Dims d, const double *__r
 }
 
 void launch_resid_flagged(const Dims &d, const Bufs &b, const DrawsDev &dr, int64_t iter, hipStream_t s) {
-    const double *Gps = dr.Gps + ((size_t)(iter - dr.first_iter) * d.g + d.shard0) * d.P;
+    const double *Gps = lam_draws_at(d, b, dr, iter, false).Gps;
     // tiles are flagged rarely (the reference's transients and excursions): 16 blocks per shard walk them
     // (one block per tile cost ~6 us of dispatch per iteration at c4 with every block exiting at once)
     const dim3 grid(std::min(d.PP / 32, 16), d.G);
@@ -191,9 +153,7 @@ void launch_resid_flagged(const Dims &d, const Bufs &b, const DrawsDev &dr, int6
 }
 
 void launch_resid(const Dims &d, const Bufs &b, const DrawsDev &dr, int64_t iter, hipStream_t s, bool gen) {
-    const double *Gps;
-    if (gen) Gps = lam_gen_plan(d, b.ldraw).Gps;   // the generated fused chain: k_wcol's buffer
-    else Gps = dr.Gps + ((size_t)(iter - dr.first_iter) * d.g + d.shard0) * d.P;
+    const double *Gps = lam_draws_at(d, b, dr, iter, gen).Gps;
     if (d.kp == KP && (size_t)d.NP * d.PP * 8 < ((size_t)1 << 31)) {   // k_resid64's buffer offsets are 32-bit
         hipLaunchKernelGGL(k_resid64, dim3((d.PP + 63) / 64, d.G), dim3(64 * RW), 0, s, d, b.Y, b.X, b.Z, b.Lam, Gps,
                            b.ps, b.omega);

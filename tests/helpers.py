@@ -111,6 +111,17 @@ def elem_rel_err(a, b):
     return float(np.max(np.abs(a - b) / np.abs(b))) if b.size else 0.0
 
 
+def ps_direct_err(got, template, Yd, hyper, draws):
+    """ps / omega of one iteration vs dc:169-171 as written (the faithful loop's update_ps with that
+    iteration's `draws`) on got's own eta and Lambda: the worst row, unscaled relative.  `template` is
+    any oracle state of the case's shape (copied)."""
+    st = template.copy()
+    for f in ("eta", "Lambda"):
+        getattr(st, f)[...] = np.asarray(got[f], dtype=np.float64).reshape(getattr(st, f).shape)
+    F.update_ps(st, Yd, hyper, draws)
+    return max(elem_rel_err(got["ps"], st.ps), elem_rel_err(got["omega"], st.omega))
+
+
 def residual_rounding_bound(got, Yd):
     """Per-row bound on the rounding error of dc:169's residual evaluation at the state `got` (MATLAB
     layout), relative to ps_j: Ytil_ij = Yd_ij - sum_k eta_ik Lambda_jk carries |delta_ij| <= (K + 1) eps

@@ -32,11 +32,11 @@ ps and omega (dc:168-172), at every iteration of every case: per row, UNSCALED r
 applied to the GPU's own eta and Lambda; the oracle chain takes the residual too
 (oracle.vectorised direct=True).  Two modes, c1-c4 each:
   exact    DCFM_FLAG_EXACT_RESIDUAL: every loading row's ps, omega from the direct residual on the
-           device (k_resid, resid.hip);
+           device (k_resid64 for K <= 32, k_resid above: resid.hip);
   default  the throughput path: SS_j by the identity yy_j - 2 lam_j.C_j + lam_j E lam_j' inside the
            loading-row kernel, except where its cancellation could cost more than ~1e3 eps (the
-           kappa guard in lambda.h): those waves take the direct residual for their 8 rows
-           (resid_rows8, same launch).  At c2's second
+           kappa guard, ss_identity_reject in resid.h): those waves take the direct residual for their
+           8 rows (resid_rows8 in resid.h, same launch).  At c2's second
            iteration the identity alone is 1.3e-10 off (kappa_j ~ 1e6: its error grows like
            kappa_j eps, the residual's like sqrt(kappa_j) eps); the guard sends those rows to the
            residual; the wide path (c4, K = 100) has the same guard, its rejected rows' 32-row tiles
@@ -44,12 +44,13 @@ applied to the GPU's own eta and Lambda; the oracle chain takes the residual too
   guard_all DCFM_FLAG_GUARD_ALL: the guard rejects every row, so every row goes through the default
            path's own fallback (c2: resid_rows8 inside k_lambda; c4: every tile through
            k_resid_flagged) -- the code the default path runs only in transients, at the same bar.
+           tests/test_gpu_resid_paths.py pins the same paths against each other at small shapes.
 """
 import numpy as np
 import pytest
 
-from helpers import (STATE_CMP, make_case, rel_err, sigma_stripe_from_lower, stacked_draws, stagewise_errors,
-                     state_dict)
+from helpers import (STATE_CMP, make_case, ps_direct_err, rel_err, sigma_stripe_from_lower, stacked_draws,
+                     stagewise_errors, state_dict)
 from oracle import vectorised as V
 
 pytestmark = pytest.mark.gpu
@@ -84,17 +85,6 @@ def _sigma_err(smp, SigL, p, w=2048):
 BW_TOL = 1e-13    # per-row backward error of the loading draw (helpers.loading_backward_error)
 
 
-def _ps_direct_err(got, start_it, D, c, it):
-    """ps / omega of one iteration vs dc:169-171 as written on got's own eta and Lambda."""
-    from helpers import elem_rel_err
-    from oracle import dc_oracle as F
-    st = start_it.copy()
-    for f in ("eta", "Lambda"):
-        getattr(st, f)[...] = np.asarray(got[f], dtype=np.float64).reshape(getattr(st, f).shape)
-    F.update_ps(st, D.Yd, c["hyper"], c["src"].iteration(it))
-    return max(elem_rel_err(got["ps"], st.ps), elem_rel_err(got["omega"], st.omega))
-
-
 @pytest.mark.parametrize("name,mode", CASES)
 def test_baseline_shape_parity(dcfm, name, mode):
     n, p, g, K, stagewise = CONFIGS[name]
@@ -118,7 +108,7 @@ def test_baseline_shape_parity(dcfm, name, mode):
             SigL = V.run_chain(D, ref, c["rho"], c["hyper"], c["src"].iteration, it, 1,
                                burnin, mcmc, thin, SigLower=SigL, direct=True)
             got = smp.get_state()
-            e = _ps_direct_err(got, start, D, c, it)
+            e = ps_direct_err(got, start, D.Yd, c["hyper"], c["src"].iteration(it))
             assert e < TOL, f"{name} {mode} iter {it}: ps / omega vs dc:169 residual, per row {e:.3e} (bar {TOL:.0e})"
             if it > 1 and stagewise:
                 errs, bw, _ = stagewise_errors(start, got, D, c["rho"], c["hyper"], c["src"].iteration(it))
@@ -169,7 +159,7 @@ def test_c5_sweep_parity(dcfm, record_property):
                 direct=True)
     errs = {f: rel_err(got[f], getattr(ref, f)) for f in STATE_CMP}
     stage, bw, _ = stagewise_errors(start, got, D, c["rho"], c["hyper"], c["src"].iteration(1))
-    ps_row = _ps_direct_err(got, start, D, c, 1)
+    ps_row = ps_direct_err(got, start, D.Yd, c["hyper"], c["src"].iteration(1))
     record_property("c5_state_rel_err", errs)
     record_property("c5_stage_rel_err", {**stage, "lambda_bw": bw, "ps_direct_per_row": ps_row})
     print("C5_PARITY", {k: f"{v:.2e}" for k, v in {**errs, **{"stage_" + s: e for s, e in stage.items()},

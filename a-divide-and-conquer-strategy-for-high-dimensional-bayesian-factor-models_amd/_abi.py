@@ -50,7 +50,7 @@ EXPORTS = (
     "dcfm_saved_samples", "dcfm_sigma_error", "dcfm_set_profiling", "dcfm_set_profiling_mask", "dcfm_set_profiling_stride", "dcfm_get_kernel_stats",
     "dcfm_kernel_name",
     "dcfm_rng_fill", "dcfm_rng_fill_rows", "dcfm_set_data_raw", "dcfm_get_data", "dcfm_count_nonzero_columns",
-    "dcfm_set_trace", "dcfm_get_trace", "dcfm_init_state",
+    "dcfm_set_trace", "dcfm_get_trace", "dcfm_init_state", "dcfm_sigma_apply", "dcfm_sigma_eigs",
 )
 
 
@@ -121,6 +121,9 @@ def load_library(path: Path | None = None):
         "dcfm_get_sigma_moment": (C.c_int, [vp, C.c_int32, _DP]),
         "dcfm_saved_samples": (C.c_int64, [vp]),
         "dcfm_sigma_error": (C.c_int, [vp, _DP, C.c_int32, _DP, C.c_int32, C.c_uint64, _DP]),
+        "dcfm_sigma_apply": (C.c_int, [vp, _DP, C.c_int32, _DP, _DP]),
+        "dcfm_sigma_eigs": (C.c_int, [vp, C.c_int32, C.c_double, C.c_int32, C.c_uint64, _DP, _DP, _DP,
+                                      C.POINTER(C.c_int32)]),
         "dcfm_set_profiling": (C.c_int, [vp, C.c_int]),
         "dcfm_set_profiling_mask": (C.c_int, [vp, C.c_uint32]),
         "dcfm_set_profiling_stride": (C.c_int, [vp, C.c_int32]),

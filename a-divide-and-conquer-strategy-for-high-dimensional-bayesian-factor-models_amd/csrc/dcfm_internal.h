@@ -253,6 +253,12 @@ int sigma_err_splits(int p);
 void launch_sigma_err(const double *S, int p, const double *U, int R, const double *sdiag, const double *v,
                       int T0, int T1, bool first, double *y, double *fro, double *tru, double *out,
                       hipStream_t s);
+// sigma_apply.hip: Y (p x nv column-major, nv <= 32) = this rank's tile rows [T0, T1) of the mirrored
+// Sigmaout times V (p x nv column-major); each stored tile read once.  scratch: sigma_apply_scratch
+// doubles (the tiles' partial panels, summed in a fixed order by a second kernel)
+size_t sigma_apply_scratch(int T0, int T1, int nv);
+void launch_sigma_apply(const double *S, int p, int T0, int T1, const double *V, int nv, double *scratch, double *Y,
+                        hipStream_t s);
 // ingest.hip: dc:31-34 column nnz counts; dc:50-59 partition + standardise into Y / yy
 void launch_nnz_cols(const double *Y, int n, long long p, int *nnz, hipStream_t s);
 void launch_stdize(const Dims &d, const double *Yraw, const long long *cols, double *Y, double *yy, double *sd,

@@ -178,4 +178,12 @@ inline int numeric_status(dcfm_handle *h) {
     return DCFM_OK;
 }
 
+// host generator of the seeded Krylov starts (dcfm_sigma_error, dcfm_sigma_eigs)
+inline uint64_t splitmix64(uint64_t &x) {
+    uint64_t z = (x += 0x9E3779B97F4A7C15ull);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
 #pragma GCC visibility pop

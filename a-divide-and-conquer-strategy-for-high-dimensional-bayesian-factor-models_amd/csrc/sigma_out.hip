@@ -176,12 +176,6 @@ static double tridiag_extreme(const std::vector<double> &a, const std::vector<do
     }
     return 0.5 * (lo + hi);
 }
-static uint64_t splitmix64(uint64_t &x) {
-    uint64_t z = (x += 0x9E3779B97F4A7C15ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
 
 int dcfm_sigma_error(dcfm_handle *h, const double *U, int32_t r, const double *sdiag, int32_t iters,
                      uint64_t seed, double out[3]) {

@@ -134,7 +134,8 @@ def local_state(state: dict, s0: int, gl: int) -> dict:
 
 def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hyper(),
                   init_draws=None, iter_draws=None, nranks=1, rank=0, device=0, comm_uid=None,
-                  asm_batch=0, return_info=False, device_ingest=True, device_init=True, return_sd=False):
+                  asm_batch=0, return_info=False, device_ingest=True, device_init=True, return_sd=False,
+                  n_components=0):
     """Sigmaout = divideconquer(Y,g,k,BURNIN,MCMC,thin,rho)   (divideconquer.m:1).
 
     ``device_ingest`` (default): the zero-column scan and the partition/standardisation
@@ -151,6 +152,12 @@ def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hy
     (DCFM_FLAG_SIGMA_M2) and return ``(Sigmaout, Sigmasd)`` — or ``(Sigmaout, Sigmasd, info)`` with
     ``return_info`` — where Sigmasd is the p x p posterior standard deviation of every entry over
     the saved samples, in Sigmaout's coordinates.
+
+    ``n_components`` > 0: also the leading principal components of Sigmaout, found on the device
+    (Sampler.sigma_eigs: ``values``, ``vectors`` p x n_components, ``resid``, ``passes``,
+    ``converged``), appended to the returned tuple after Sigmasd (if requested) and before info.  The
+    vectors are in Sigmaout's coordinates; ``unpermute_vectors`` takes them back to the input's.
+    With several ranks every rank takes part and returns the same dict.
     """
     t0 = time.perf_counter()                                     # dc:29 tic
     if device_ingest:
@@ -192,10 +199,13 @@ def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hy
         smp.run(1, N)                                            # dc:90-197
         Sigmaout = smp.get_sigma()
         Sigmasd = smp.get_sigma_moment("sd") if return_sd else None
+        pcs = smp.sigma_eigs(int(n_components)) if n_components > 0 else None
     finally:
         smp.close()
     elapsed = time.perf_counter() - t0                           # dc:200 toc
     out = (Sigmaout, Sigmasd) if return_sd else (Sigmaout,)
+    if n_components > 0:
+        out += (pcs,)
     if return_info:
         out += ({"varind": np.asarray(init.varind), "keep": keep, "n": n, "p": p, "P": P,
                  "K": K, "N": N, "seconds": elapsed},)
@@ -237,4 +247,24 @@ def unpermute_sigma(S, keep, varind, p_orig, sd=None, fill=0.0):
         S = S * sd[:, None] * sd[None, :]
     out = np.full((p_orig, p_orig), fill, dtype=np.float64)
     out[np.ix_(cols, cols)] = S
+    return out
+
+
+def unpermute_vectors(V, keep, varind, p_orig, sd=None, fill=0.0):
+    """Vectors in Sigmaout's coordinates (rows of V: (p,) or (p, r), e.g. the ``vectors`` of
+    ``Sampler.sigma_eigs``) back in the input's column order: row a goes to row cols[a] with
+    cols = output_columns(keep, varind); rows of dropped (all-zero, dc:36-39) columns get
+    ``fill`` -- the row analogue of ``unpermute_sigma``.  With ``sd`` (the sample standard
+    deviations of the kept columns in Sigmaout's order) row a is scaled by sd_a: the vectors are
+    then loadings in data units (directions of the unstandardised covariance's factor
+    diag(sd) V) and are no longer orthonormal."""
+    V = np.asarray(V, dtype=np.float64)
+    cols = output_columns(keep, varind)
+    if V.shape[0] != cols.size:
+        raise ValueError(f"V must have p = {cols.size} rows, got {V.shape}")
+    if sd is not None:
+        sd = np.asarray(sd, dtype=np.float64).reshape(-1)
+        V = V * (sd if V.ndim == 1 else sd[:, None])
+    out = np.full((p_orig,) + V.shape[1:], fill, dtype=np.float64)
+    out[cols] = V
     return out

@@ -259,6 +259,47 @@ class Sampler:
         fro, tru, op = (float(x) for x in out)
         return {"fro": fro, "op": op, "fro_rel": fro / tru if tru > 0 else float("nan"), "truth_fro": tru}
 
+    def sigma_apply(self, V, return_ms=False):
+        """Sigmaout @ V on the device (dcfm_sigma_apply): V is (p,) or (p, nv) in Sigmaout's permuted,
+        standardised coordinates, the result has V's shape and equals ``get_sigma() @ V`` without the
+        matrix leaving HBM.  Any nv; the kernel serves 32 columns per pass.  Collective when
+        nranks > 1: every rank calls it with the same V and receives the full product.
+        ``return_ms``: also the kernels' accumulated device time in milliseconds."""
+        p = self.P * self.g
+        V = np.asarray(V, dtype=np.float64)
+        if V.ndim not in (1, 2) or V.shape[0] != p:
+            raise ValueError(f"V must be (p,) or (p, nv) with p = {p}, got {V.shape}")
+        V2 = _f64F(V.reshape(p, -1))
+        out = np.zeros(V2.shape, dtype=np.float64, order="F")
+        ms = C.c_double(0.0)
+        self._check(self.lib.dcfm_sigma_apply(self.h, _ptr(V2), V2.shape[1], _ptr(out),
+                                              C.byref(ms) if return_ms else None))
+        out = out.reshape(V.shape, order="F")
+        return (out, ms.value) if return_ms else out
+
+    def sigma_eigs(self, r, tol=1e-10, max_passes=None, seed=1, vectors=True) -> dict:
+        """The r largest eigenpairs of Sigmaout (1 <= r <= min(32, p)) by a block Krylov iteration on
+        sigma_apply (dcfm_sigma_eigs); Sigmaout stays in HBM.  Returns ``values`` (r, descending),
+        ``vectors`` (p x r, orthonormal columns, the entry of largest magnitude of each positive; None
+        with ``vectors=False``), ``resid`` (||Sigma v_i - lambda_i v_i||_2 from a real pass on the
+        returned vectors), ``passes`` (block applies of the iteration) and ``converged`` = all resid
+        <= tol * values[0].  Reaching ``max_passes`` (default ceil(p / b) + 1 with b = min(32, p),
+        enough for the basis to span everything) unconverged is not an error: read ``resid``.
+        Collective when nranks > 1; every rank returns the same bits."""
+        p = self.P * self.g
+        r = int(r)
+        b = min(32, p)
+        if max_passes is None:
+            max_passes = -(-p // b) + 1
+        vals = np.zeros(max(r, 1))
+        res = np.zeros(max(r, 1))
+        vec = np.zeros((p, max(r, 1)), dtype=np.float64, order="F") if vectors else None
+        npass = C.c_int32(0)
+        self._check(self.lib.dcfm_sigma_eigs(self.h, r, float(tol), int(max_passes), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                             _ptr(vals), _ptr(vec) if vectors else None, _ptr(res), C.byref(npass)))
+        return {"values": vals, "vectors": vec, "resid": res, "passes": int(npass.value),
+                "converged": bool(np.all(res <= float(tol) * vals[0]))}
+
     def saved_samples(self) -> int:
         return int(self.lib.dcfm_saved_samples(self.h))
 

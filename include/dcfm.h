@@ -229,6 +229,49 @@ int  dcfm_get_sigma_moment(dcfm_handle *h, int32_t which, double *out);
 int  dcfm_sigma_error(dcfm_handle *h, const double *U, int32_t r, const double *s, int32_t iters,
                       uint64_t seed, double out[3]);
 
+/* ---- Sigmaout as a linear operator -----------------------------------------
+ * Sigmaout is too big to move (1.6 GB of stored triangle at c3, 80 GB over the ranks at c5), so
+ * the products a covariance is estimated for -- projections, quadratic forms, principal
+ * components -- are taken where it lies.
+ *
+ * dcfm_sigma_apply: out = Sigmaout * V.  V and out are p x nv column-major host arrays (p = P*g,
+ * nv >= 1, in Sigmaout's permuted, standardised coordinates); the result equals
+ * dcfm_get_sigma(h) times V (the mean accumulator, with the read-out's effsamp scaling), up to the
+ * rounding of a length-p dot product in another summation order.  One kernel pass serves up to 32
+ * columns and reads every stored 128 x 128 tile of the lower triangle once (fp64 MFMA, both the
+ * tile and its mirror from the one read), so a pass moves about 4 p^2 bytes whatever nv <= 32 is;
+ * a larger nv runs in chunks of 32 inside the call.  No atomics: the same inputs give the same bits
+ * on every call.  dev_ms (nullable): the accumulated device time of the kernel passes.
+ * Collective when nranks > 1: every rank calls it with the same V, multiplies the tiles it owns,
+ * and receives the full product (an all-reduce of p x nv).  Works with and without
+ * DCFM_FLAG_SIGMA_M2 and never reads the second moment.  Device scratch (the V and out blocks and
+ * the tiles' partial panels, about p^2 nv' / 128 doubles with nv' = 16 or 32) is allocated inside
+ * the call and freed before it returns.
+ * Errors: NULL handle ("null handle") or NULL V / out ("null argument"), nv < 1: DCFM_ERR_INVALID. */
+int  dcfm_sigma_apply(dcfm_handle *h, const double *V, int32_t nv, double *out, double *dev_ms);
+/* dcfm_sigma_eigs: the r largest eigenpairs of Sigmaout, 1 <= r <= min(32, p), by a block Krylov
+ * (block Lanczos) iteration with Rayleigh-Ritz: a seeded normal start block of width b = min(32, p),
+ * one dcfm_sigma_apply pass per step, the new block re-orthogonalised twice against the whole basis
+ * and within itself (columns falling below 1e-13 of their norm are dropped, so a rank-deficient block
+ * puts no NaN into the basis).  It stops when max_i resid_i <= tol * lambda_1, after max_passes
+ * passes, or when the basis spans all p dimensions (then the result is exact); reaching max_passes
+ * unconverged is NOT an error -- the call returns DCFM_OK and the caller reads resid.
+ *   evals[r]    descending
+ *   evecs       nullable; p x r column-major, orthonormal columns, the entry of largest magnitude of
+ *               each column positive (lowest index on ties): comparable across runs and ranks
+ *   resid[r]    ||Sigmaout v_i - lambda_i v_i||_2 from a real dcfm_sigma_apply pass on the returned
+ *               vectors (not the Ritz estimate)
+ *   passes      nullable; block applies of the iteration (the residual pass on the r vectors, and
+ *               a pass that checked a not-yet-converged candidate, are not counted)
+ * The basis (p x passes*b doubles, twice) and the projected eigenproblem (at most max_passes*b wide,
+ * solved by csrc/symeig.h: no LAPACK) stay on the host, as dcfm_sigma_error's Lanczos basis does;
+ * Sigmaout never leaves HBM.  Collective when nranks > 1: every rank runs the same host arithmetic
+ * on the same all-reduced bytes and returns identical results.
+ * Errors (DCFM_ERR_INVALID): NULL handle, NULL evals / resid, r outside 1..min(32, p), tol <= 0,
+ * max_passes < 1, no saved sample yet (dcfm_saved_samples == 0). */
+int  dcfm_sigma_eigs(dcfm_handle *h, int32_t r, double tol, int32_t max_passes, uint64_t seed,
+                     double *evals, double *evecs, double *resid, int32_t *passes);
+
 /* ---- chain trace (convergence diagnostics across chains) ----
  * dcfm_set_trace(h, cap): record one row per iteration of later dcfm_run calls, up to cap
  * rows (0 = off, the default; resets the count).  Row = this rank's local-shard sums

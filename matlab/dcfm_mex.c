@@ -20,6 +20,12 @@
  *                                         mean, second moment or standard deviation of Sigma's
  *                                         entries ('m2', 'sd' need cfg.sigma_m2 = 1), p x p or
  *                                         the columns col0 .. col0+ncols-1 (0-based), p x ncols
+ *   Y = dcfm_mex('sigma_apply', h, V)     Y = Sigmaout * V on the device, V p x nv (any nv >= 1), in
+ *                                         Sigmaout's permuted, standardised coordinates
+ *   [d, V, res] = dcfm_mex('sigma_eigs', h, r[, tol, max_passes, seed])   the r <= 32 largest eigenpairs
+ *                                         of Sigmaout (block Krylov on sigma_apply): d r x 1 descending,
+ *                                         V p x r orthonormal, res r x 1 = ||Sigmaout v - d v||_2;
+ *                                         defaults tol 1e-10, max_passes ceil(p / min(32, p)) + 1, seed 1
  *   e = dcfm_mex('error', h, U, s, iters)[||S-S0||_F, ||S0||_F, ||S-S0||_2] vs S0 = UU' + diag(s)
  *   dcfm_mex('set_trace', h, cap); T = dcfm_mex('get_trace', h)     chain trace (count x 4)
  *   dcfm_mex('destroy', h)
@@ -262,6 +268,44 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
             mexErrMsgIdAndTxt("dcfm:arg", "columns [%g, %g) outside 0..p = %lld", c0, c0 + nc, (long long)p);
         plhs[0] = mxCreateDoubleMatrix((mwSize)p, (mwSize)nc, mxREAL);
         ck(t->h, dcfm_get_sigma_moment_cols(t->h, which, (int64_t)c0, (int64_t)nc, mxGetDoubles(plhs[0])));
+    } else if (!strcmp(cmd, "sigma_apply")) {        /* Y = dcfm_mex('sigma_apply', h, V) */
+        nargs(nrhs, 3, cmd);
+        slot *t = get(prhs[1]);
+        const int64_t p = t->P * t->g;               /* the row count the library reads and writes */
+        const mxArray *V = prhs[2];
+        if (!mxIsDouble(V) || mxIsComplex(V) || (int64_t)mxGetM(V) != p || mxGetN(V) < 1 || mxGetN(V) > 2147483647 ||
+            (int64_t)mxGetNumberOfElements(V) != p * (int64_t)mxGetN(V))
+            mexErrMsgIdAndTxt("dcfm:arg", "V must be a real double p x nv matrix, p = %lld, nv >= 1", (long long)p);
+        plhs[0] = mxCreateDoubleMatrix((mwSize)p, mxGetN(V), mxREAL);
+        ck(t->h, dcfm_sigma_apply(t->h, mxGetDoubles(V), (int32_t)mxGetN(V), mxGetDoubles(plhs[0]), NULL));
+    } else if (!strcmp(cmd, "sigma_eigs")) {         /* [d, V, res] = dcfm_mex('sigma_eigs', h, r[, tol, max_passes, seed]) */
+        if (nrhs < 3 || nrhs > 6)
+            mexErrMsgIdAndTxt("dcfm:nargs", "'%s' takes 2 to 5 arguments, got %d", cmd, nrhs - 1);
+        /* the arguments that need no handle first: a malformed call never reaches the library */
+        const double rr = scalar(prhs[2], "r");
+        const double tol = nrhs > 3 ? scalar(prhs[3], "tol") : 1e-10;
+        const double mp = nrhs > 4 ? scalar(prhs[4], "max_passes") : 0;
+        const double sd = nrhs > 5 ? scalar(prhs[5], "seed") : 1;
+        if (rr < 1 || rr > 32 || rr != (double)(int32_t)rr) mexErrMsgIdAndTxt("dcfm:arg", "r must be an integer in 1..32");
+        if (!(tol > 0)) mexErrMsgIdAndTxt("dcfm:arg", "tol must be > 0");
+        if (nrhs > 4 && (mp < 1 || mp > 2147483647.0 || mp != (double)(int32_t)mp))
+            mexErrMsgIdAndTxt("dcfm:arg", "max_passes must be a positive integer");
+        if (sd < 0 || sd > 9007199254740992.0 || sd != (double)(uint64_t)sd)
+            mexErrMsgIdAndTxt("dcfm:arg", "seed must be a non-negative integer");
+        slot *t = get(prhs[1]);
+        const int64_t p = t->P * t->g, b = p < 32 ? p : 32;
+        if (rr > (double)p) mexErrMsgIdAndTxt("dcfm:arg", "r = %g exceeds p = %lld", rr, (long long)p);
+        const int32_t r = (int32_t)rr, passes = nrhs > 4 ? (int32_t)mp : (int32_t)((p + b - 1) / b + 1);
+        mxArray *o[3];
+        o[0] = mxCreateDoubleMatrix((mwSize)r, 1, mxREAL);
+        o[1] = mxCreateDoubleMatrix((mwSize)p, (mwSize)r, mxREAL);
+        o[2] = mxCreateDoubleMatrix((mwSize)r, 1, mxREAL);
+        ck(t->h, dcfm_sigma_eigs(t->h, r, tol, passes, (uint64_t)sd, mxGetDoubles(o[0]), mxGetDoubles(o[1]),
+                                 mxGetDoubles(o[2]), NULL));
+        for (int q = 0; q < 3; ++q) {
+            if (q < (nlhs < 1 ? 1 : nlhs)) plhs[q] = o[q];
+            else mxDestroyArray(o[q]);
+        }
     } else if (!strcmp(cmd, "destroy")) {
         nargs(nrhs, 2, cmd);
         slot *t = get(prhs[1]);

@@ -51,6 +51,7 @@ EXPORTS = (
     "dcfm_kernel_name",
     "dcfm_rng_fill", "dcfm_rng_fill_rows", "dcfm_set_data_raw", "dcfm_get_data", "dcfm_count_nonzero_columns",
     "dcfm_set_trace", "dcfm_get_trace", "dcfm_init_state", "dcfm_sigma_apply", "dcfm_sigma_eigs",
+    "dcfm_sigma_solve",
 )
 
 
@@ -124,6 +125,8 @@ def load_library(path: Path | None = None):
         "dcfm_sigma_apply": (C.c_int, [vp, _DP, C.c_int32, _DP, _DP]),
         "dcfm_sigma_eigs": (C.c_int, [vp, C.c_int32, C.c_double, C.c_int32, C.c_uint64, _DP, _DP, _DP,
                                       C.POINTER(C.c_int32)]),
+        "dcfm_sigma_solve": (C.c_int, [vp, _DP, C.c_int32, C.c_double, C.c_int32, _DP, _DP, C.POINTER(C.c_int32),
+                                       _DP, _DP]),
         "dcfm_set_profiling": (C.c_int, [vp, C.c_int]),
         "dcfm_set_profiling_mask": (C.c_int, [vp, C.c_uint32]),
         "dcfm_set_profiling_stride": (C.c_int, [vp, C.c_int32]),

@@ -2,42 +2,12 @@
 // sigma_apply.hip) and dcfm_sigma_eigs (the largest eigenpairs by a block Krylov iteration on it).
 // Sigmaout never leaves HBM; the tall-skinny algebra of the iteration runs on the host, as
 // dcfm_sigma_error keeps its Lanczos basis there.
-#include "handle.h"
+#include "sigma_op.h"
 #include "symeig.h"
 
 #include <new>
 
 namespace {
-
-constexpr int APPLY_NB = 32;   // right-hand sides per kernel pass
-
-// device scratch of the apply passes of one call: V and Y blocks (p x 32 each) and the kernel's
-// partial panels; allocated inside the call and freed before it returns
-struct ApplyScratch {
-    double *dev = nullptr, *dV = nullptr, *dY = nullptr, *part = nullptr;
-    hipEvent_t ea = nullptr, eb = nullptr;
-    int alloc(dcfm_handle *h, int nv_max, const char *who) {
-        const size_t P = (size_t)h->d.p, w = (size_t)std::min(nv_max, APPLY_NB);
-        const size_t nd = 2 * P * w + sigma_apply_scratch(h->b.T0, h->b.T1, (int)w);
-        void *q = nullptr;
-        const hipError_t e = hipMalloc(&q, std::max<size_t>(nd, 1) * sizeof(double));
-        if (e != hipSuccess) return fail(h, DCFM_ERR_ALLOC, "%s: %zu doubles of scratch: %s", who, nd, hipGetErrorString(e));
-        dev = static_cast<double *>(q);
-        dV = dev;
-        dY = dV + P * w;
-        part = dY + P * w;
-        ea = get_event(h);
-        eb = get_event(h);
-        return DCFM_OK;
-    }
-    void release(dcfm_handle *h) {
-        if (dev) (void)hipFree(dev);
-        if (ea) h->evpool.push_back(ea);
-        if (eb) h->evpool.push_back(eb);
-        dev = nullptr;
-        ea = eb = nullptr;
-    }
-};
 
 // out (p x nv column-major, host) = Sigmaout V, in blocks of <= 32 columns; collective over ranks
 // (every rank's tiles, summed on CH_ASM: every rank gets the full product).  ms (nullable)
@@ -63,18 +33,6 @@ int apply_host(dcfm_handle *h, ApplyScratch &sc, const double *V, int nv, double
         }
     }
     return DCFM_OK;
-}
-
-// arguments are checked, the device selected, the streams drained and the sentinel read, in the
-// order of dcfm_sigma_error; `code` carries an earlier argument failure
-int enter(dcfm_handle *h, int code, const char *who) {
-    if (code == DCFM_OK) {
-        const hipError_t e = hipSetDevice(h->cfg.device);
-        if (e != hipSuccess) code = fail(h, DCFM_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-    }
-    sync_all(h);
-    if (code == DCFM_OK) code = numeric_status(h);
-    return code;
 }
 
 double dot(const double *a, const double *b, size_t n) {
@@ -119,7 +77,7 @@ int dcfm_sigma_apply(dcfm_handle *h, const double *V, int32_t nv, double *out, d
     int code = DCFM_OK;
     if (!V || !out) code = fail(h, DCFM_ERR_INVALID, "null argument");
     else if (nv < 1) code = fail(h, DCFM_ERR_INVALID, "sigma_apply: nv = %d < 1", nv);
-    code = enter(h, code, "sigma_apply");
+    code = sigma_op_enter(h, code, "sigma_apply");
     ApplyScratch sc;
     if (code == DCFM_OK) code = sc.alloc(h, nv, "sigma_apply");   // before agree(): fails on every rank
     if (int rc = agree(h, code)) {
@@ -144,7 +102,7 @@ int dcfm_sigma_eigs(dcfm_handle *h, int32_t r, double tol, int32_t max_passes, u
     else if (!(tol > 0.0)) code = fail(h, DCFM_ERR_INVALID, "sigma_eigs: tol = %g <= 0", tol);
     else if (max_passes < 1) code = fail(h, DCFM_ERR_INVALID, "sigma_eigs: max_passes = %d < 1", max_passes);
     else if (h->saved < 1) code = fail(h, DCFM_ERR_INVALID, "sigma_eigs: no saved sample yet");
-    code = enter(h, code, "sigma_eigs");
+    code = sigma_op_enter(h, code, "sigma_eigs");
     ApplyScratch sc;
     // basis Q and its image W = Sigmaout Q (p x m column-major, m <= mcap), reserved here so that an
     // allocation failure fails the call on every rank before the first collective

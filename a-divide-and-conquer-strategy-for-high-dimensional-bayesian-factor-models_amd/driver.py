@@ -135,7 +135,7 @@ def local_state(state: dict, s0: int, gl: int) -> dict:
 def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hyper(),
                   init_draws=None, iter_draws=None, nranks=1, rank=0, device=0, comm_uid=None,
                   asm_batch=0, return_info=False, device_ingest=True, device_init=True, return_sd=False,
-                  n_components=0):
+                  n_components=0, rhs=None):
     """Sigmaout = divideconquer(Y,g,k,BURNIN,MCMC,thin,rho)   (divideconquer.m:1).
 
     ``device_ingest`` (default): the zero-column scan and the partition/standardisation
@@ -158,6 +158,17 @@ def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hy
     ``converged``), appended to the returned tuple after Sigmasd (if requested) and before info.  The
     vectors are in Sigmaout's coordinates; ``unpermute_vectors`` takes them back to the input's.
     With several ranks every rank takes part and returns the same dict.
+
+    ``rhs``: right-hand sides B, (p_orig,) or (p_orig, nv) with one row per column of Y in the input's
+    column order.  B is taken into Sigmaout's coordinates (``permute_vectors`` without sd: the rows of
+    dropped all-zero columns fall away) and Sigmaout x = B is solved on the device
+    (Sampler.sigma_solve with its defaults: tol 1e-10, at most min(2 p, 1000) steps); a dict ``{"x", "relres", "iters",
+    "quad"}``, x in Sigmaout's coordinates, is appended to the returned tuple after the
+    ``n_components`` dict (if requested) and before info.  Sigmaout is the standardised covariance S;
+    the unstandardised one is D S D with D = diag(sd) (the sample standard deviations of the kept
+    columns in Sigmaout's order), so its precision applied to b is D^-1 S^-1 D^-1 b:
+    ``x = sigma_solve(permute_vectors(b, keep, varind, sd=sd))``, then
+    ``unpermute_vectors(x / sd[:, None], keep, varind, p_orig)``.
     """
     t0 = time.perf_counter()                                     # dc:29 tic
     if device_ingest:
@@ -200,12 +211,18 @@ def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hy
         Sigmaout = smp.get_sigma()
         Sigmasd = smp.get_sigma_moment("sd") if return_sd else None
         pcs = smp.sigma_eigs(int(n_components)) if n_components > 0 else None
+        sol = None
+        if rhs is not None:
+            x, si = smp.sigma_solve(permute_vectors(rhs, keep, init.varind), return_info=True)
+            sol = {"x": x, "relres": si["relres"], "iters": si["iters"], "quad": si["quad"]}
     finally:
         smp.close()
     elapsed = time.perf_counter() - t0                           # dc:200 toc
     out = (Sigmaout, Sigmasd) if return_sd else (Sigmaout,)
     if n_components > 0:
         out += (pcs,)
+    if rhs is not None:
+        out += (sol,)
     if return_info:
         out += ({"varind": np.asarray(init.varind), "keep": keep, "n": n, "p": p, "P": P,
                  "K": K, "N": N, "seconds": elapsed},)
@@ -267,4 +284,23 @@ def unpermute_vectors(V, keep, varind, p_orig, sd=None, fill=0.0):
         V = V * (sd if V.ndim == 1 else sd[:, None])
     out = np.full((p_orig,) + V.shape[1:], fill, dtype=np.float64)
     out[cols] = V
+    return out
+
+
+def permute_vectors(B, keep, varind, sd=None):
+    """Vectors in the input's column order (rows of B: (p_orig,) or (p_orig, nv), one per column of
+    Y) into Sigmaout's coordinates: row a of the result is row cols[a] of B with
+    cols = output_columns(keep, varind); the rows of dropped (all-zero, dc:36-39) columns fall away.
+    The exact inverse of ``unpermute_vectors`` on the kept rows.  With ``sd`` (the sample standard
+    deviations of the kept columns in Sigmaout's order) row a is divided by sd_a, which undoes
+    ``unpermute_vectors(..., sd=sd)`` -- and is the D^-1 b of the unstandardised precision
+    D^-1 S^-1 D^-1 b (``divideconquer(..., rhs=)``)."""
+    B = np.asarray(B, dtype=np.float64)
+    cols = output_columns(keep, varind)
+    if B.ndim not in (1, 2) or B.shape[0] <= int(cols.max(initial=-1)):
+        raise ValueError(f"B must have one row per input column (more than {int(cols.max(initial=-1))}), got {B.shape}")
+    out = B[cols]
+    if sd is not None:
+        sd = np.asarray(sd, dtype=np.float64).reshape(-1)
+        out = out / (sd if B.ndim == 1 else sd[:, None])
     return out

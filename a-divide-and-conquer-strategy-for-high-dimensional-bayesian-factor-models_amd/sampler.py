@@ -300,6 +300,45 @@ class Sampler:
         return {"values": vals, "vectors": vec, "resid": res, "passes": int(npass.value),
                 "converged": bool(np.all(res <= float(tol) * vals[0]))}
 
+    def sigma_solve(self, B, tol=1e-10, max_iter=None, return_info=False):
+        """Sigmaout^{-1} B on the device (dcfm_sigma_solve): B is (p,) or (p, nv) in Sigmaout's permuted,
+        standardised coordinates and X has B's shape, ``get_sigma() @ X = B`` without the matrix leaving
+        HBM.  Conjugate gradients, every column on its own (alpha, beta and stop test per column), 32
+        columns per pass and the whole iteration on the device.  A column stops when its recurrence
+        residual is <= tol * ||B_c||, or after ``max_iter`` steps (default min(2 p, 1000)); reaching
+        ``max_iter`` is not an error: read ``relres``.  Collective when nranks > 1: every rank calls it
+        with the same B and receives the same X.
+        ``return_info``: also a dict with ``relres`` (||B_c - Sigma X_c|| / ||B_c|| from a real pass on
+        the returned X; 0 for a zero column), ``iters`` (CG steps of each column), ``quad`` (B_c' X_c,
+        the quadratic form b' Sigma^{-1} b), ``converged`` (``iters < max_iter``: the column was stopped
+        by its own test, or by the zero-denominator guard, before the cap -- a column that met the test
+        on the very last allowed step counts as not converged; ``relres`` is the measure) and ``ms``
+        (the kernels' accumulated device time).  The per-column entries have shape (nv,), or are
+        scalars for a (p,) B."""
+        p = self.P * self.g
+        B = np.asarray(B, dtype=np.float64)
+        if B.ndim not in (1, 2) or B.shape[0] != p:
+            raise ValueError(f"B must be (p,) or (p, nv) with p = {p}, got {B.shape}")
+        B2 = _f64F(B.reshape(p, -1))
+        nv = B2.shape[1]
+        if max_iter is None:
+            max_iter = min(2 * p, 1000)
+        X = np.zeros(B2.shape, dtype=np.float64, order="F")
+        relres, quad = np.zeros(max(nv, 1)), np.zeros(max(nv, 1))
+        iters = np.zeros(max(nv, 1), dtype=np.int32)
+        ms = C.c_double(0.0)
+        self._check(self.lib.dcfm_sigma_solve(self.h, _ptr(B2), nv, float(tol), int(max_iter), _ptr(X), _ptr(relres),
+                                              iters.ctypes.data_as(C.POINTER(C.c_int32)), _ptr(quad),
+                                              C.byref(ms) if return_info else None))
+        X = X.reshape(B.shape, order="F")
+        if not return_info:
+            return X
+        info = {"relres": relres, "iters": iters.astype(np.int64), "quad": quad, "converged": iters < int(max_iter)}
+        if B.ndim == 1:
+            info = {k: v[0].item() for k, v in info.items()}
+        info["ms"] = ms.value
+        return X, info
+
     def saved_samples(self) -> int:
         return int(self.lib.dcfm_saved_samples(self.h))
 

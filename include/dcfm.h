@@ -271,6 +271,36 @@ int  dcfm_sigma_apply(dcfm_handle *h, const double *V, int32_t nv, double *out, 
  * max_passes < 1, no saved sample yet (dcfm_saved_samples == 0). */
 int  dcfm_sigma_eigs(dcfm_handle *h, int32_t r, double tol, int32_t max_passes, uint64_t seed,
                      double *evals, double *evecs, double *resid, int32_t *passes);
+/* dcfm_sigma_solve: X = Sigmaout^{-1} B by conjugate gradients on dcfm_sigma_apply's pass, with the
+ * whole iteration on the device.  B and X are p x nv column-major host arrays (nv >= 1, Sigmaout's
+ * permuted, standardised coordinates); Sigmaout X = B for the operator dcfm_sigma_apply multiplies
+ * by, which is symmetric positive definite once a sample is saved (a mean of Lambda C Lambda' +
+ * diag(omega), omega > 0) with a diagonal of about 1, so the iteration is plain CG, no preconditioner.
+ * The columns are solved independently and in lock-step: each has its own alpha, beta and stop test,
+ * and one pass serves up to 32 of them (this is not O'Leary's block CG: no nv x nv solves, no
+ * rank-deficiency breakdown); a larger nv runs in chunks of 32 inside the call.  Between the upload
+ * of a chunk of B and the download of its X no p-length vector crosses the bus: per step the host
+ * reads the columns' done flags.
+ * A column stops when its recurrence residual satisfies ||r_c|| <= tol ||B_c||, or after max_iter
+ * steps; reaching max_iter is NOT an error -- the call returns DCFM_OK and the caller reads relres.
+ * A stopped column is frozen (its X, r, p untouched by later steps).  A column with B_c = 0 returns
+ * X_c = 0 exactly with iters 0, and a column whose p' Sigmaout p is <= 0 or not finite is frozen at
+ * its current iterate, so no NaN from a division reaches X.
+ *   relres[nv]  ||B_c - Sigmaout X_c||_2 / ||B_c||_2 from a real pass on the returned X (not the
+ *               recurrence's estimate); 0 where B_c = 0
+ *   iters[nv]   nullable; CG steps taken by each column
+ *   quad[nv]    nullable; B_c' X_c, formed on the device: the quadratic form b' Sigmaout^{-1} b
+ *   dev_ms      nullable; accumulated device time of the call's kernels (passes and panel kernels)
+ * No atomics: the same inputs give the same bits, and a column's bits do not depend on which other
+ * columns share its call.  Collective when nranks > 1: every rank calls with the same B, keeps the
+ * panels replicated and runs the same vector kernels on the same all-reduced bytes of the pass, so
+ * the stop decisions (and the number of collective calls) are identical and every rank receives
+ * identical X.  Works with and without DCFM_FLAG_SIGMA_M2.  Device scratch (dcfm_sigma_apply's plus
+ * three p x min(nv, 32) panels) is allocated inside the call and freed before it returns.
+ * Errors (DCFM_ERR_INVALID): NULL handle ("null handle"), NULL B / X / relres ("null argument"),
+ * nv < 1, tol <= 0 or not finite, max_iter < 1, no saved sample yet (dcfm_saved_samples == 0). */
+int  dcfm_sigma_solve(dcfm_handle *h, const double *B, int32_t nv, double tol, int32_t max_iter,
+                      double *X, double *relres, int32_t *iters, double *quad, double *dev_ms);
 
 /* ---- chain trace (convergence diagnostics across chains) ----
  * dcfm_set_trace(h, cap): record one row per iteration of later dcfm_run calls, up to cap

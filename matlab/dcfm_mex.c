@@ -26,6 +26,11 @@
  *                                         of Sigmaout (block Krylov on sigma_apply): d r x 1 descending,
  *                                         V p x r orthonormal, res r x 1 = ||Sigmaout v - d v||_2;
  *                                         defaults tol 1e-10, max_passes ceil(p / min(32, p)) + 1, seed 1
+ *   [X, relres, iters] = dcfm_mex('sigma_solve', h, B[, tol, max_iter])   X = Sigmaout \ B on the device
+ *                                         (conjugate gradients, every column on its own), B p x nv in
+ *                                         Sigmaout's coordinates; relres nv x 1 = ||B - Sigmaout X|| / ||B||
+ *                                         per column from a real pass, iters nv x 1 the CG steps taken;
+ *                                         defaults tol 1e-10, max_iter min(2 p, 1000)
  *   e = dcfm_mex('error', h, U, s, iters)[||S-S0||_F, ||S0||_F, ||S-S0||_2] vs S0 = UU' + diag(s)
  *   dcfm_mex('set_trace', h, cap); T = dcfm_mex('get_trace', h)     chain trace (count x 4)
  *   dcfm_mex('destroy', h)
@@ -36,6 +41,7 @@
 
 #include "mex.h"
 #include "dcfm.h"
+#include <float.h>
 #include <stdint.h>
 #include <string.h>
 
@@ -302,6 +308,40 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         o[2] = mxCreateDoubleMatrix((mwSize)r, 1, mxREAL);
         ck(t->h, dcfm_sigma_eigs(t->h, r, tol, passes, (uint64_t)sd, mxGetDoubles(o[0]), mxGetDoubles(o[1]),
                                  mxGetDoubles(o[2]), NULL));
+        for (int q = 0; q < 3; ++q) {
+            if (q < (nlhs < 1 ? 1 : nlhs)) plhs[q] = o[q];
+            else mxDestroyArray(o[q]);
+        }
+    } else if (!strcmp(cmd, "sigma_solve")) {        /* [X, relres, iters] = dcfm_mex('sigma_solve', h, B[, tol, max_iter]) */
+        if (nrhs < 3 || nrhs > 5)
+            mexErrMsgIdAndTxt("dcfm:nargs", "'%s' takes 2 to 4 arguments, got %d", cmd, nrhs - 1);
+        /* the arguments that need no handle first: a malformed call never reaches the library */
+        const double tol = nrhs > 3 ? scalar(prhs[3], "tol") : 1e-10;
+        const double mi = nrhs > 4 ? scalar(prhs[4], "max_iter") : 0;
+        if (!(tol > 0) || tol > DBL_MAX) mexErrMsgIdAndTxt("dcfm:arg", "tol must be a positive finite number");
+        if (nrhs > 4 && (mi < 1 || mi > 2147483647.0 || mi != (double)(int32_t)mi))
+            mexErrMsgIdAndTxt("dcfm:arg", "max_iter must be a positive integer");
+        slot *t = get(prhs[1]);
+        const int64_t p = t->P * t->g;               /* the row count the library reads and writes */
+        const mxArray *B = prhs[2];
+        if (!mxIsDouble(B) || mxIsComplex(B) || (int64_t)mxGetM(B) != p || mxGetN(B) < 1 || mxGetN(B) > 2147483647 ||
+            (int64_t)mxGetNumberOfElements(B) != p * (int64_t)mxGetN(B))
+            mexErrMsgIdAndTxt("dcfm:arg", "B must be a real double p x nv matrix, p = %lld, nv >= 1", (long long)p);
+        const int32_t nv = (int32_t)mxGetN(B), max_iter = nrhs > 4 ? (int32_t)mi : (int32_t)(2 * p < 1000 ? 2 * p : 1000);
+        mxArray *o[3];
+        o[0] = mxCreateDoubleMatrix((mwSize)p, (mwSize)nv, mxREAL);
+        o[1] = mxCreateDoubleMatrix((mwSize)nv, 1, mxREAL);
+        o[2] = mxCreateDoubleMatrix((mwSize)nv, 1, mxREAL);
+        /* the library's int32 steps land in the front half of o[2]'s own storage (nothing to free if the
+         * call fails) and are widened in place from the back */
+        double *itd = mxGetDoubles(o[2]);
+        ck(t->h, dcfm_sigma_solve(t->h, mxGetDoubles(B), nv, tol, max_iter, mxGetDoubles(o[0]), mxGetDoubles(o[1]),
+                                  (int32_t *)itd, NULL, NULL));
+        for (int32_t c = nv - 1; c >= 0; --c) {
+            int32_t v;
+            memcpy(&v, (const char *)itd + (size_t)c * sizeof v, sizeof v);
+            itd[c] = (double)v;
+        }
         for (int q = 0; q < 3; ++q) {
             if (q < (nlhs < 1 ? 1 : nlhs)) plhs[q] = o[q];
             else mxDestroyArray(o[q]);

@@ -144,6 +144,24 @@ inline LamDraws lam_draws_at(const Dims &d, const Bufs &b, const DrawsDev &dr, i
 // k_wcol shard sum of A
 constexpr int XSUM_BLOCKS = 8;
 constexpr int TRACE_SLICES = 16;       // k_trace_part blocks per local shard (slices of its loading rows)
+// Probe draws (probes.hip): at most PROBE_NV_MAX probe vectors; k_probes runs probe_slices(G) blocks per
+// local shard, each a fixed slice of its loading rows: about one block per CU, so that a few big shards
+// (c4: 8 of 1250 rows, K = 100) are split 32 ways and many small ones (c3: 64 of 312 rows) only 4 ways --
+// a slice's partial is K nv + nv^2 doubles, more than the ~10 rows a 32-way slice of c3 would read
+constexpr int PROBE_NV_MAX = 32, PROBE_SLICES_MAX = 32, PROBE_FAN = 8;   // FAN: shard terms added per group
+inline int probe_slices(int G) { return G >= 256 ? 1 : (256 / G < PROBE_SLICES_MAX ? 256 / G : PROBE_SLICES_MAX); }
+// device buffers of dcfm_set_probes: V [G * P][nv] this rank's rows of the probe block (row-major),
+// part [G][slices][ts] slice partials, term [G][ts] shard terms and gterm [ceil(G / PROBE_FAN)][ts] group
+// sums, each [W (K x nv) | D (nv x nv)] with ts = K nv + nv^2, ticket: last-arrival tickets of the
+// shards, the groups and the rank, draws [capacity][slot]:
+// slot = nv^2 (one rank: V' Sigma(s) V itself) or ts (several ranks: [W_r | D_r])
+struct Probes {
+    const double *V;
+    double *part, *term, *gterm, *draws;
+    unsigned *ticket;
+    int nv, slices;
+    size_t slot;
+};
 // Bufs::sync: [0] the X operators (k_xdraw, several ranks), [1] spare, [2, 2 + 256) chunk counters of the A sum, [SYNC_ZM, SYNC_ZM + G) the
 // per-shard Z-operator counters (the fused W pass draws Z once its shard's operators are out)
 constexpr int SYNC_ZM = 2 + 256;
@@ -267,6 +285,8 @@ void launch_stdize(const Dims &d, const double *Yraw, const long long *cols, dou
 // row [G][4]; scratch = trace_scratch_doubles(G) zeroed doubles (slice partials + per-shard tickets)
 inline size_t trace_scratch_doubles(int G) { return (size_t)G * TRACE_SLICES * 4 + (G + 1) / 2; }
 void launch_trace(const Dims &d, const Bufs &b, const double *tau_cur, double *scratch, double *row, hipStream_t s);
+// probes.hip: draw s of V' Sigma V from the current Lambda, omega (after launch_save, same stream)
+void launch_probes(const Dims &d, const Bufs &b, const Probes &pr, int64_t s, hipStream_t st);
 // init.hip: dc:68-87 initial state from Philox (iteration-0 counters), delta/tau buffer 0
 void launch_init_state(const Dims &d, const Bufs &b, hipStream_t s);
 // kernels.hip: one iteration's variates into the draw buffers (side-stream layouts)

@@ -72,6 +72,10 @@ struct dcfm_handle {
     // per-iteration chain trace (dcfm_set_trace): [scratch | rows [trace_cap][G][4]] (trace.hip)
     double *trace = nullptr;
     int64_t trace_cap = 0, trace_n = 0;
+    // per-sample probe draws (dcfm_set_probes, probes.hip): one allocation, null when off
+    double *probe_mem = nullptr;
+    Probes probes{};
+    int64_t probe_cap = 0, probe_n = 0;
     bool prof = false;
     uint32_t prof_mask = 0;       // kernel ids (bit DCFM_K_*) timed with events
     int prof_stride = 1;          // time one in prof_stride launches of each (dcfm_set_profiling_stride)

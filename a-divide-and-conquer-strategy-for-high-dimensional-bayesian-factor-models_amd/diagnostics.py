@@ -81,3 +81,26 @@ def summarize(traces, fields=TRACE_FIELDS) -> dict:
     """{field: {"rhat": R, "ess": E}} for a (chains, iterations, 4) device trace."""
     r, e = split_rhat(traces), ess(traces)
     return {f: {"rhat": float(r[i]), "ess": float(e[i])} for i, f in enumerate(fields)}
+
+
+def summarize_probes(draws, q=(0.025, 0.5, 0.975)) -> dict:
+    """Posterior summaries of the per-sample probe draws ``Q[s] = V' Sigma(s) V`` (``Sampler.probe_draws``,
+    shape (S, nv, nv); a single (nv, nv) draw is taken as S = 1).  Returns ``mean`` and ``sd`` (nv x nv, over
+    the draws; sd in the population form), ``quantiles`` (len(q), nv, nv) at the levels ``q`` (NumPy's
+    default linear interpolation), ``corr`` (S, nv, nv), the correlation matrix of every draw
+    ``Q_ab / sqrt(Q_aa Q_bb)`` -- a nonlinear functional, so it is formed per draw and not from the mean;
+    NaN where a probe's variance is not positive, e.g. an all-zero probe -- and ``corr_quantiles``
+    (len(q), nv, nv).  Contrasts, variance ratios and other functionals follow the same way from
+    ``draws``."""
+    Q = np.asarray(draws, dtype=np.float64)
+    if Q.ndim == 2:
+        Q = Q[None]
+    if Q.ndim != 3 or Q.shape[1] != Q.shape[2] or Q.shape[0] < 1:
+        raise ValueError(f"draws must be (S, nv, nv) with S >= 1, got {Q.shape}")
+    qs = np.asarray(q, dtype=np.float64).reshape(-1)
+    d = np.diagonal(Q, axis1=1, axis2=2)                        # (S, nv) variances of the projections
+    with np.errstate(divide="ignore", invalid="ignore"):
+        s = np.sqrt(np.where(d > 0, d, np.nan))
+        corr = Q / (s[:, :, None] * s[:, None, :])
+    return {"mean": Q.mean(axis=0), "sd": Q.std(axis=0), "quantiles": np.quantile(Q, qs, axis=0),
+            "corr": corr, "corr_quantiles": np.quantile(corr, qs, axis=0), "q": qs}

@@ -135,7 +135,7 @@ def local_state(state: dict, s0: int, gl: int) -> dict:
 def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hyper(),
                   init_draws=None, iter_draws=None, nranks=1, rank=0, device=0, comm_uid=None,
                   asm_batch=0, return_info=False, device_ingest=True, device_init=True, return_sd=False,
-                  n_components=0, rhs=None):
+                  n_components=0, rhs=None, probes=None):
     """Sigmaout = divideconquer(Y,g,k,BURNIN,MCMC,thin,rho)   (divideconquer.m:1).
 
     ``device_ingest`` (default): the zero-column scan and the partition/standardisation
@@ -169,6 +169,17 @@ def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hy
     columns in Sigmaout's order), so its precision applied to b is D^-1 S^-1 D^-1 b:
     ``x = sigma_solve(permute_vectors(b, keep, varind, sd=sd))``, then
     ``unpermute_vectors(x / sd[:, None], keep, varind, p_orig)``.
+
+    ``probes``: probe vectors V, (p_orig,) or (p_orig, nv) with nv <= 32 and one row per column of Y in
+    the input's column order.  V is taken into Sigmaout's coordinates (``permute_vectors`` without sd:
+    the rows of dropped all-zero columns fall away) and ``V' Sigma(s) V`` is recorded on the device for
+    every saved sample s (Sampler.set_probes with its default capacity, mcmc // thin); a dict
+    ``{"draws", "mean", "sd"}`` -- draws (S, nv, nv), their mean and their standard deviation over the
+    draws (population form, as Sigmasd) -- is appended to the returned tuple after the ``rhs`` dict (if
+    requested) and before info.  ``diagnostics.summarize_probes`` gives quantiles and the per-draw
+    correlations.  For the unstandardised covariance D S D probe with D v:
+    ``Sampler.set_probes(permute_vectors(v, keep, varind) * sd[:, None])``, sd the sample standard
+    deviations of the kept columns in Sigmaout's order.
     """
     t0 = time.perf_counter()                                     # dc:29 tic
     if device_ingest:
@@ -207,6 +218,8 @@ def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hy
             smp.set_state(local_state(state, s0, gl))
         if iter_draws is not None:
             smp.set_draws(iter_draws, 1, N)
+        if probes is not None:
+            smp.set_probes(permute_vectors(probes, keep, init.varind))
         smp.run(1, N)                                            # dc:90-197
         Sigmaout = smp.get_sigma()
         Sigmasd = smp.get_sigma_moment("sd") if return_sd else None
@@ -215,6 +228,10 @@ def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hy
         if rhs is not None:
             x, si = smp.sigma_solve(permute_vectors(rhs, keep, init.varind), return_info=True)
             sol = {"x": x, "relres": si["relres"], "iters": si["iters"], "quad": si["quad"]}
+        prb = None
+        if probes is not None:
+            q = smp.probe_draws()
+            prb = {"draws": q, "mean": q.mean(axis=0), "sd": q.std(axis=0)}
     finally:
         smp.close()
     elapsed = time.perf_counter() - t0                           # dc:200 toc
@@ -223,6 +240,8 @@ def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hy
         out += (pcs,)
     if rhs is not None:
         out += (sol,)
+    if probes is not None:
+        out += (prb,)
     if return_info:
         out += ({"varind": np.asarray(init.varind), "keep": keep, "n": n, "p": p, "P": P,
                  "K": K, "N": N, "seconds": elapsed},)

@@ -358,6 +358,39 @@ class Sampler:
         self._check(self.lib.dcfm_get_trace(self.h, _ptr(out), C.byref(cnt)))
         return out[:cnt.value].copy()
 
+    # -- per-sample probe draws ------------------------------------------------------
+    def set_probes(self, V, capacity=None):
+        """Record ``V' Sigma(s) V`` for every saved sample s of later runs (dcfm_set_probes): V is
+        (p,) or (p, nv), 1 <= nv <= 32, in Sigmaout's permuted, standardised coordinates (every rank
+        passes the same V).  Up to ``capacity`` draws are held (default ``mcmc // thin``); later saved
+        samples are not recorded.  Calling it again replaces V and resets the count; ``set_probes(None)``
+        turns the recording off and frees its buffers."""
+        if V is None:
+            self._check(self.lib.dcfm_set_probes(self.h, None, 0, 0))
+            self._probe_nv = self._probe_cap = 0
+            return
+        p = self.P * self.g
+        V = np.asarray(V, dtype=np.float64)
+        if V.ndim not in (1, 2) or V.shape[0] != p:
+            raise ValueError(f"V must be (p,) or (p, nv) with p = {p}, got {V.shape}")
+        V2 = _f64F(V.reshape(p, -1))
+        if capacity is None:
+            capacity = int(self.cfg.mcmc) // int(self.cfg.thin)
+        self._check(self.lib.dcfm_set_probes(self.h, _ptr(V2), V2.shape[1], int(capacity)))
+        self._probe_nv = V2.shape[1] if int(capacity) > 0 else 0
+        self._probe_cap = int(capacity)
+
+    def probe_draws(self) -> np.ndarray:
+        """The recorded draws, shape (S, nv, nv): ``draws[s] = V' Sigma(s) V`` in saved-sample order, the
+        per-sample matrix without effsamp scaling (``draws.sum(0) / effsamp = V' Sigmaout V``), every
+        slice symmetric bit for bit.  (0, 0, 0) when no probes are set.  Collective when nranks > 1:
+        every rank calls it and receives the same bytes."""
+        nv, cap = getattr(self, "_probe_nv", 0), getattr(self, "_probe_cap", 0)
+        cnt = C.c_int64(0)
+        out = np.zeros((max(cap, 1), nv, nv), dtype=np.float64)          # one (collective) call
+        self._check(self.lib.dcfm_get_probe_draws(self.h, _ptr(out), C.byref(cnt)))
+        return out[:cnt.value].copy()
+
     # -- measurement -----------------------------------------------------------------
     def set_profiling(self, on: bool):
         self._check(self.lib.dcfm_set_profiling(self.h, 1 if on else 0))

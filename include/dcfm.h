@@ -312,6 +312,45 @@ int  dcfm_sigma_solve(dcfm_handle *h, const double *B, int32_t nv, double tol, i
 int  dcfm_set_trace(dcfm_handle *h, int64_t capacity);
 int  dcfm_get_trace(dcfm_handle *h, double *out, int64_t *count);
 
+/* ---- per-sample draws of V' Sigma V (posterior uncertainty of any functional) ----
+ * The read-outs above describe the posterior mean of Sigma, and DCFM_FLAG_SIGMA_M2 one standard
+ * deviation per entry.  A quantity that is not a single entry -- the variance v' Sigma v of a portfolio
+ * or contrast, a correlation Sigma_ab / sqrt(Sigma_aa Sigma_bb), a ratio of variances, a credible
+ * interval for any of them -- needs its value per saved sample.  With Sigma(s) the matrix dc:182-192
+ * builds from saved sample s, the library records Q(:,:,s) = V' * Sigma(s) * V for a caller-chosen block
+ * V, from one read of Lambda and V per saved sample (Sigma(s) is never formed): with W_m = Lambda_m' V_m,
+ * W = sum_m W_m,  V' Sigma(s) V = rho W'W + sum_m [(1 - rho) W_m'W_m + V_m' diag(omega_m) V_m].
+ *
+ * dcfm_set_probes: V is a p x nv column-major host array (p = P*g, 1 <= nv <= 32) in Sigmaout's permuted,
+ * standardised coordinates, as for dcfm_sigma_apply; every rank passes the same full V and keeps the rows
+ * of its own shards on the device.  From the next dcfm_run on, every saved sample (mod(iter,thin)==0 &&
+ * iter>burnin, dc:180) records one draw until `capacity` draws are held; later saved samples are not
+ * recorded (as dcfm_set_trace).  Calling it again replaces V and resets the count.  capacity == 0 (V may
+ * then be NULL, nv is ignored) turns the feature off and frees its buffers; until a call with
+ * capacity > 0 nothing is allocated and nothing is launched.  Needs neither data nor state nor a
+ * communicator and is not collective.  The kernel runs behind k_save on the sweep stream and its device
+ * time is booked under DCFM_K_SAVE.  No floating-point atomics and fixed summation orders: the same
+ * inputs give the same bits on every run.
+ * Device bytes: 8 (P g_local nv + capacity * slot + scratch), with slot = nv^2 on one rank (the draw
+ * itself) and K nv + nv^2 on several (the rank's partial W and its partial of the bracket above), and
+ * scratch = (g_local (s + 1) + ceil(g_local / 8)) (K nv + nv^2) doubles of slice, shard and shard-group
+ * partials (s = min(32, max(1, 256 / g_local)) slices per shard) plus a ticket word for each.
+ * Errors (DCFM_ERR_INVALID, a block set before stays as it was): NULL handle ("null handle"), NULL V with
+ * capacity > 0 ("null argument"), nv outside 1..32, capacity < 0, a non-finite entry in V.
+ *
+ * dcfm_get_probe_draws: count (required) receives the number of draws held; out (nullable) the nv x nv x
+ * count column-major array Q above, in saved-sample order.  Sigma(s) is the per-sample matrix itself,
+ * without the effsamp scaling: sum(Q,3) / effsamp equals V' * Sigmaout * V up to rounding.  Every slice
+ * is symmetric bit for bit (one triangle computed, then mirrored).  Blocks (synchronises the sweep
+ * stream) and does not disturb a later dcfm_run.  With nranks > 1 it is collective: every rank calls it,
+ * the ranks' partials of all draws travel in one all-gather (nothing p-length crosses the bus), are
+ * summed in rank order, and every rank receives identical bytes.  With no probes set *count = 0 and
+ * DCFM_OK.  After a run that ended in DCFM_ERR_NUMERIC it returns what the device holds (NaN included),
+ * as dcfm_get_state_raw.  Errors (DCFM_ERR_INVALID): NULL handle ("null handle"), NULL count
+ * ("null argument"). */
+int  dcfm_set_probes(dcfm_handle *h, const double *V, int32_t nv, int64_t capacity);
+int  dcfm_get_probe_draws(dcfm_handle *h, double *out, int64_t *count);
+
 /* ---- measurement --------------------------------------------------------- */
 /* Per-kernel HIP-event timing on the handle's stream (off by default).
  * Kernel ids: DCFM_K_* below.  Times are accumulated device milliseconds. */

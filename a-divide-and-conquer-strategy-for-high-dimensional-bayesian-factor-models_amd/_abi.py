@@ -51,7 +51,8 @@ EXPORTS = (
     "dcfm_kernel_name",
     "dcfm_rng_fill", "dcfm_rng_fill_rows", "dcfm_set_data_raw", "dcfm_get_data", "dcfm_count_nonzero_columns",
     "dcfm_set_trace", "dcfm_get_trace", "dcfm_init_state", "dcfm_sigma_apply", "dcfm_sigma_eigs",
-    "dcfm_sigma_solve", "dcfm_set_probes", "dcfm_get_probe_draws",
+    "dcfm_sigma_solve", "dcfm_set_probes", "dcfm_get_probe_draws", "dcfm_set_precision_probes",
+    "dcfm_get_precision_draws",
 )
 
 
@@ -129,6 +130,8 @@ def load_library(path: Path | None = None):
                                        _DP, _DP]),
         "dcfm_set_probes": (C.c_int, [vp, _DP, C.c_int32, C.c_int64]),
         "dcfm_get_probe_draws": (C.c_int, [vp, _DP, C.POINTER(C.c_int64)]),
+        "dcfm_set_precision_probes": (C.c_int, [vp, _DP, C.c_int32, C.c_int64]),
+        "dcfm_get_precision_draws": (C.c_int, [vp, _DP, _DP, C.POINTER(C.c_int64)]),
         "dcfm_set_profiling": (C.c_int, [vp, C.c_int]),
         "dcfm_set_profiling_mask": (C.c_int, [vp, C.c_uint32]),
         "dcfm_set_profiling_stride": (C.c_int, [vp, C.c_int32]),

@@ -353,6 +353,7 @@ void dcfm_destroy(dcfm_handle *h) {
     if (h->draws_mem) (void)hipFree(h->draws_mem);
     if (h->trace) (void)hipFree(h->trace);
     if (h->probe_mem) (void)hipFree(h->probe_mem);
+    if (h->prec_mem) (void)hipFree(h->prec_mem);
     if (h->sasm && h->sasm != h->stream) (void)hipStreamDestroy(h->sasm);
     if (h->side && h->side != h->stream) (void)hipStreamDestroy(h->side);
     if (h->sdraw && h->sdraw != h->stream) (void)hipStreamDestroy(h->sdraw);
@@ -473,6 +474,7 @@ static int save_sample(dcfm_handle *h, int64_t it) {
         KTimer t(h, DCFM_K_SAVE, s);
         launch_save(h->d, b, b.Lb[h->lb], b.wsum[h->lb], h->batch, s, b.wslot[h->lb], h->B);
         if (h->probe_n < h->probe_cap) launch_probes(h->d, b, h->probes, h->probe_n++, s);   // dcfm_set_probes
+        if (h->prec_n < h->prec_cap) launch_precision(h->d, b, h->prec, h->prec_n++, s);   // dcfm_set_precision_probes
     }
     HIPC(h, hipGetLastError());
     h->batch += 1;

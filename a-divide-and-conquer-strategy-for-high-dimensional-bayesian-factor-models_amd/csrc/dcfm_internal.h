@@ -162,6 +162,27 @@ struct Probes {
     int nv, slices;
     size_t slot;
 };
+// Precision draws (precision.hip): V' Sigma(s)^{-1} V and log det Sigma(s) per saved sample.  k_precision runs
+// precision_slices blocks per local shard; a slice's partial is the lower 16x16 tiles of the weighted Gram of
+// [Lambda_m | V_m] (wp^2 / 2 doubles, wp = K + nv padded to 16), so a slice reads at least wp / 2 rows
+__host__ __device__ constexpr int precision_tiles(int K, int nv) { return ((K + nv + 15) / 16) * ((K + nv + 15) / 16 + 1) / 2; }
+inline int precision_slices(int G, int P, int K, int nv) {
+    const int wp = (K + nv + 15) / 16 * 16, rows = wp / 2 > 8 ? wp / 2 : 8, cap = P / rows > 1 ? P / rows : 1;
+    return probe_slices(G) < cap ? probe_slices(G) : cap;
+}
+// device buffers of dcfm_set_precision_probes, w = K + nv: V [G * P][nv] as Probes::V, part [G][slices][ps] slice
+// partials (ps = 256 precision_tiles + 1: the tiles in the MFMA C/D layout, then sum log omega), gram [G][w][w]
+// the shards' folded Gram (both triangles), term [G][ts] shard terms, gterm [ceil(G / PROBE_FAN)][ts] group sums
+// and rsum [ts] the rank's sum, each [H | F (K x w, row-major) | q (nv x nv) | ld] with ts = K w + nv^2 + 1,
+// xs [K][nv] the solve S^{-1} F, ticket as Probes::ticket, draws [capacity][slot]: slot = nv^2 + 1 (one rank:
+// the draw and its log det) or ts (several ranks: the rank's sum)
+struct Precision {
+    const double *V;
+    double *part, *gram, *term, *gterm, *rsum, *xs, *draws;
+    unsigned *ticket;
+    int nv, slices;
+    size_t slot, lds;
+};
 // Bufs::sync: [0] the X operators (k_xdraw, several ranks), [1] spare, [2, 2 + 256) chunk counters of the A sum, [SYNC_ZM, SYNC_ZM + G) the
 // per-shard Z-operator counters (the fused W pass draws Z once its shard's operators are out)
 constexpr int SYNC_ZM = 2 + 256;
@@ -287,6 +308,8 @@ inline size_t trace_scratch_doubles(int G) { return (size_t)G * TRACE_SLICES * 4
 void launch_trace(const Dims &d, const Bufs &b, const double *tau_cur, double *scratch, double *row, hipStream_t s);
 // probes.hip: draw s of V' Sigma V from the current Lambda, omega (after launch_save, same stream)
 void launch_probes(const Dims &d, const Bufs &b, const Probes &pr, int64_t s, hipStream_t st);
+// precision.hip: draw s of V' Sigma^{-1} V and log det Sigma from the current Lambda, omega (same place)
+void launch_precision(const Dims &d, const Bufs &b, const Precision &pr, int64_t s, hipStream_t st);
 // init.hip: dc:68-87 initial state from Philox (iteration-0 counters), delta/tau buffer 0
 void launch_init_state(const Dims &d, const Bufs &b, hipStream_t s);
 // kernels.hip: one iteration's variates into the draw buffers (side-stream layouts)

@@ -76,6 +76,10 @@ struct dcfm_handle {
     double *probe_mem = nullptr;
     Probes probes{};
     int64_t probe_cap = 0, probe_n = 0;
+    // per-sample precision draws (dcfm_set_precision_probes, precision.hip): the same, independent of the probes
+    double *prec_mem = nullptr;
+    Precision prec{};
+    int64_t prec_cap = 0, prec_n = 0;
     bool prof = false;
     uint32_t prof_mask = 0;       // kernel ids (bit DCFM_K_*) timed with events
     int prof_stride = 1;          // time one in prof_stride launches of each (dcfm_set_profiling_stride)

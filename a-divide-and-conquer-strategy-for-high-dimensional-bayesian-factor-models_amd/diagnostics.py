@@ -91,7 +91,8 @@ def summarize_probes(draws, q=(0.025, 0.5, 0.975)) -> dict:
     ``Q_ab / sqrt(Q_aa Q_bb)`` -- a nonlinear functional, so it is formed per draw and not from the mean;
     NaN where a probe's variance is not positive, e.g. an all-zero probe -- and ``corr_quantiles``
     (len(q), nv, nv).  Contrasts, variance ratios and other functionals follow the same way from
-    ``draws``."""
+    ``draws``.  The precision draws ``V' Sigma(s)^-1 V`` of ``Sampler.precision_draws`` have the same shape
+    and go through unchanged (``corr`` is then the partial-correlation-like ratio of the projected precision)."""
     Q = np.asarray(draws, dtype=np.float64)
     if Q.ndim == 2:
         Q = Q[None]
@@ -104,3 +105,24 @@ def summarize_probes(draws, q=(0.025, 0.5, 0.975)) -> dict:
         corr = Q / (s[:, :, None] * s[:, None, :])
     return {"mean": Q.mean(axis=0), "sd": Q.std(axis=0), "quantiles": np.quantile(Q, qs, axis=0),
             "corr": corr, "corr_quantiles": np.quantile(corr, qs, axis=0), "q": qs}
+
+
+def heldout_log_density(Q, logdet, p) -> dict:
+    """Held-out Gaussian log density from the precision draws (``Sampler.precision_draws``): with
+    ``Q[s] = V' Sigma(s)^-1 V`` (S, nv, nv), ``logdet[s] = log det Sigma(s)`` (S,) and every column of V one
+    centred, standardised held-out row in Sigmaout's coordinates (p entries), returns ``per_sample``
+    (S, nv), ``-(p log 2 pi + logdet[s] + Q[s, c, c]) / 2``, the log density of row c under sample s;
+    ``lppd`` (nv,), the log of the mean over s of the densities (log-mean-exp, shifted by the maximum so
+    that it neither overflows nor underflows) -- the log pointwise predictive density, by which ``k``,
+    ``g`` and ``rho`` can be compared on held-out rows -- and ``total``, the sum of lppd.  Standardised
+    units: a density in the original units subtracts ``sum(log sd)``."""
+    Q = np.asarray(Q, dtype=np.float64)
+    ld = np.asarray(logdet, dtype=np.float64).reshape(-1)
+    if Q.ndim != 3 or Q.shape[1] != Q.shape[2] or Q.shape[0] < 1 or ld.shape[0] != Q.shape[0]:
+        raise ValueError(f"Q must be (S, nv, nv) and logdet (S,) with S >= 1, got {Q.shape} and {ld.shape}")
+    per = -0.5 * (p * np.log(2.0 * np.pi) + ld[:, None] + np.diagonal(Q, axis1=1, axis2=2))
+    top = per.max(axis=0)
+    safe = np.where(np.isfinite(top), top, 0.0)
+    with np.errstate(divide="ignore"):
+        lppd = safe + np.log(np.mean(np.exp(per - safe), axis=0))
+    return {"per_sample": per, "lppd": lppd, "total": float(lppd.sum())}

@@ -135,7 +135,7 @@ def local_state(state: dict, s0: int, gl: int) -> dict:
 def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hyper(),
                   init_draws=None, iter_draws=None, nranks=1, rank=0, device=0, comm_uid=None,
                   asm_batch=0, return_info=False, device_ingest=True, device_init=True, return_sd=False,
-                  n_components=0, rhs=None, probes=None):
+                  n_components=0, rhs=None, probes=None, precision_probes=None):
     """Sigmaout = divideconquer(Y,g,k,BURNIN,MCMC,thin,rho)   (divideconquer.m:1).
 
     ``device_ingest`` (default): the zero-column scan and the partition/standardisation
@@ -180,6 +180,18 @@ def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hy
     correlations.  For the unstandardised covariance D S D probe with D v:
     ``Sampler.set_probes(permute_vectors(v, keep, varind) * sd[:, None])``, sd the sample standard
     deviations of the kept columns in Sigmaout's order.
+
+    ``precision_probes``: probe vectors V as for ``probes`` (nv = 0, a (p_orig, 0) block, is allowed),
+    permuted exactly as ``probes`` is; ``V' Sigma(s)^-1 V`` and ``log det Sigma(s)`` are recorded on the
+    device for every saved sample s (Sampler.set_precision_probes, capacity mcmc // thin) and a dict
+    ``{"draws", "logdet", "mean", "sd"}`` -- draws (S, nv, nv), logdet (S,), mean and sd of the draws -- is
+    appended after the ``probes`` dict (if requested) and before info.  Held-out log density: a new row
+    y in the input's column order becomes the probe
+    ``permute_vectors(((y - mean) / sd)[:, None], keep, varind)`` (mean and sd the training columns'
+    sample mean and standard deviation, in the input's order), and
+    ``diagnostics.heldout_log_density(draws, logdet, p)`` gives the per-sample densities and their
+    log-mean-exp (lppd) in the standardised units; a density in the original units subtracts
+    ``sum(log sd)`` over the kept columns.
     """
     t0 = time.perf_counter()                                     # dc:29 tic
     if device_ingest:
@@ -220,6 +232,8 @@ def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hy
             smp.set_draws(iter_draws, 1, N)
         if probes is not None:
             smp.set_probes(permute_vectors(probes, keep, init.varind))
+        if precision_probes is not None:
+            smp.set_precision_probes(permute_vectors(precision_probes, keep, init.varind))
         smp.run(1, N)                                            # dc:90-197
         Sigmaout = smp.get_sigma()
         Sigmasd = smp.get_sigma_moment("sd") if return_sd else None
@@ -232,6 +246,10 @@ def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hy
         if probes is not None:
             q = smp.probe_draws()
             prb = {"draws": q, "mean": q.mean(axis=0), "sd": q.std(axis=0)}
+        prc = None
+        if precision_probes is not None:
+            q, ld = smp.precision_draws()
+            prc = {"draws": q, "logdet": ld, "mean": q.mean(axis=0), "sd": q.std(axis=0)}
     finally:
         smp.close()
     elapsed = time.perf_counter() - t0                           # dc:200 toc
@@ -242,6 +260,8 @@ def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hy
         out += (sol,)
     if probes is not None:
         out += (prb,)
+    if precision_probes is not None:
+        out += (prc,)
     if return_info:
         out += ({"varind": np.asarray(init.varind), "keep": keep, "n": n, "p": p, "P": P,
                  "K": K, "N": N, "seconds": elapsed},)

@@ -391,6 +391,42 @@ class Sampler:
         self._check(self.lib.dcfm_get_probe_draws(self.h, _ptr(out), C.byref(cnt)))
         return out[:cnt.value].copy()
 
+    # -- per-sample precision draws --------------------------------------------------
+    def set_precision_probes(self, V, capacity=None):
+        """Record ``V' Sigma(s)^-1 V`` and ``log det Sigma(s)`` for every saved sample s of later runs
+        (dcfm_set_precision_probes): V is (p,) or (p, nv), 0 <= nv <= 32, in Sigmaout's permuted,
+        standardised coordinates (every rank passes the same V); a (p, 0) block records the log
+        determinant alone.  Up to ``capacity`` draws are held (default ``mcmc // thin``).  Calling it
+        again replaces V and resets the count; ``set_precision_probes(None)`` turns the recording off and
+        frees its buffers.  Independent of ``set_probes``: both may be on at once."""
+        if V is None:
+            self._check(self.lib.dcfm_set_precision_probes(self.h, None, 0, 0))
+            self._prec_nv = self._prec_cap = 0
+            return
+        p = self.P * self.g
+        V = np.asarray(V, dtype=np.float64)
+        if V.ndim not in (1, 2) or V.shape[0] != p:
+            raise ValueError(f"V must be (p,) or (p, nv) with p = {p}, got {V.shape}")
+        V2 = _f64F(V.reshape(p, -1) if V.ndim == 1 else V)
+        if capacity is None:
+            capacity = int(self.cfg.mcmc) // int(self.cfg.thin)
+        self._check(self.lib.dcfm_set_precision_probes(self.h, _ptr(V2) if V2.shape[1] else None, V2.shape[1],
+                                                       int(capacity)))
+        self._prec_nv = V2.shape[1] if int(capacity) > 0 else 0
+        self._prec_cap = int(capacity)
+
+    def precision_draws(self):
+        """``(Q, logdet)``: Q of shape (S, nv, nv) with ``Q[s] = V' Sigma(s)^-1 V`` in saved-sample order, every
+        slice symmetric bit for bit, and logdet of shape (S,) with ``log det Sigma(s)``, Sigma(s) the
+        per-sample matrix of dc:182-192.  Shapes (0, 0, 0) and (0,) when nothing is set.  Collective when
+        nranks > 1: every rank calls it and receives the same bytes."""
+        nv, cap = getattr(self, "_prec_nv", 0), getattr(self, "_prec_cap", 0)
+        cnt = C.c_int64(0)
+        Q = np.zeros((max(cap, 1), nv, nv), dtype=np.float64)           # one (collective) call
+        ld = np.zeros(max(cap, 1), dtype=np.float64)
+        self._check(self.lib.dcfm_get_precision_draws(self.h, _ptr(Q), _ptr(ld), C.byref(cnt)))
+        return Q[:cnt.value].copy(), ld[:cnt.value].copy()
+
     # -- measurement -----------------------------------------------------------------
     def set_profiling(self, on: bool):
         self._check(self.lib.dcfm_set_profiling(self.h, 1 if on else 0))

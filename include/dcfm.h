@@ -351,6 +351,46 @@ int  dcfm_get_trace(dcfm_handle *h, double *out, int64_t *count);
 int  dcfm_set_probes(dcfm_handle *h, const double *V, int32_t nv, int64_t capacity);
 int  dcfm_get_probe_draws(dcfm_handle *h, double *out, int64_t *count);
 
+/* ---- per-sample draws of V' Sigma^{-1} V and log det Sigma (posterior of anything through the inverse) ----
+ * dcfm_sigma_solve applies the inverse of the posterior mean.  A Mahalanobis distance, a discriminant
+ * score, minimum-variance weights, a partial correlation or the held-out Gaussian log density
+ * -(p log 2 pi + log det Sigma(s) + y' Sigma(s)^{-1} y) / 2 need Sigma(s)^{-1} per saved sample.  Sigma(s) =
+ * D + rho Lbar Lbar' with D = blockdiag((1 - rho) L_m L_m' + Omega_m) is block-diagonal plus rank K, so two
+ * nested Woodbury steps give both from one weighted Gram [L_m V_m]' Omega_m^{-1} [L_m V_m] per shard, g
+ * K x K inversions and one more: one read of Lambda, omega and V per saved sample, Sigma(s) never formed, no
+ * p x p factorisation and no iteration (csrc/precision.hip has the recursion).
+ *
+ * dcfm_set_precision_probes: as dcfm_set_probes in every respect not listed here -- V p x nv column-major
+ * in Sigmaout's permuted, standardised coordinates, every rank passes the full V and keeps its own rows,
+ * recording from the next dcfm_run at every saved sample until `capacity` draws are held, a second call
+ * replaces V and resets the count, capacity == 0 turns it off and frees its buffers, nothing allocated or
+ * launched until it is on, not collective, booked under DCFM_K_SAVE, no floating-point atomics and fixed
+ * summation orders.  Differences: 0 <= nv <= 32, and with nv == 0 (V may be NULL) only log det Sigma(s) is
+ * recorded; it is independent of dcfm_set_probes: both may be on at once and neither changes the other's
+ * bits.
+ * Device bytes: 8 (P g_local nv + capacity * slot + scratch); with w = K + nv and ts = K w + nv^2 + 1 (a
+ * term [H | F | q | ld]: H K x K and q nv x nv stored square, one triangle computed and mirrored in q),
+ * slot = nv^2 + 1 on one rank (the draw and its log det) and ts on several (the rank's sum of terms), and
+ * scratch = g_local s (256 nt + 1) + g_local w^2 + (g_local + ceil(g_local / 8) + 1) ts + K nv doubles: the
+ * slice partials (nt = the lower 16 x 16 tiles of w padded to 16, s = min(the probes' s, max(1, P / max(8,
+ * wpad / 2))) slices per shard), the shards' Grams, the shard, group and rank terms and one solve, plus a
+ * ticket word per shard and group.  The kernel uses up to 8 (K^2 + 16 K) bytes + 2 KiB of LDS (146 KiB at K = 128).
+ * Errors (DCFM_ERR_INVALID, a block set before stays as it was): NULL handle ("null handle"), NULL V with
+ * capacity > 0 and nv > 0 ("null argument"), nv outside 0..32, capacity < 0, a non-finite entry in V.
+ *
+ * dcfm_get_precision_draws: count (required) receives the number of draws held; Q (nullable) the nv x nv x
+ * count array of V' Sigma(s)^{-1} V in saved-sample order, every slice symmetric bit for bit (one triangle
+ * computed, then mirrored); logdet (nullable) the count values of log det Sigma(s).  Blocks (synchronises
+ * the sweep stream) and does not disturb a later dcfm_run.  With nothing set *count = 0 and DCFM_OK.  After
+ * a run that ended in DCFM_ERR_NUMERIC it returns what the device holds: a NaN state gives NaN draws (the
+ * inversions take no data-dependent trip counts).  With nranks > 1 it is collective: every rank's sum
+ * [H_r | F_r | q_r | ld_r] of all draws travels in one all-gather, every rank adds them in rank order and
+ * closes the K x K step on the host (a plain Cholesky), and every rank receives identical bytes; one rank
+ * closes it in the kernel.  Errors (DCFM_ERR_INVALID): NULL handle ("null handle"), NULL count ("null
+ * argument"). */
+int  dcfm_set_precision_probes(dcfm_handle *h, const double *V, int32_t nv, int64_t capacity);
+int  dcfm_get_precision_draws(dcfm_handle *h, double *Q, double *logdet, int64_t *count);
+
 /* ---- measurement --------------------------------------------------------- */
 /* Per-kernel HIP-event timing on the handle's stream (off by default).
  * Kernel ids: DCFM_K_* below.  Times are accumulated device milliseconds. */

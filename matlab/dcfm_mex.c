@@ -35,6 +35,12 @@
  *                                         later runs, V p x nv (1 <= nv <= 32) in Sigmaout's coordinates;
  *                                         capacity draws are held (default mcmc / thin; 0 turns it off)
  *   Q = dcfm_mex('probe_draws', h)        the recorded draws, nv x nv x S (0 x 0 x 0 with no probes set)
+ *   dcfm_mex('set_precision_probes', h, V[, capacity])   record Q(:,:,s) = V' * inv(Sigma_s) * V and
+ *                                         logdet(s) = log(det(Sigma_s)) for every saved sample s of later runs,
+ *                                         V p x nv (0 <= nv <= 32; p x 0: the log det alone) in Sigmaout's
+ *                                         coordinates; capacity as for 'set_probes'; independent of it
+ *   [Q, logdet] = dcfm_mex('precision_draws', h)   the recorded draws, nv x nv x S and S x 1 (empty with
+ *                                         nothing set)
  *   e = dcfm_mex('error', h, U, s, iters)[||S-S0||_F, ||S0||_F, ||S-S0||_2] vs S0 = UU' + diag(s)
  *   dcfm_mex('set_trace', h, cap); T = dcfm_mex('get_trace', h)     chain trace (count x 4)
  *   dcfm_mex('destroy', h)
@@ -55,6 +61,7 @@ typedef struct {
     int64_t n, P, g, K;        /* this handle's dimensions (single rank: g_local = g) */
     int64_t mcmc, thin;        /* default capacity of 'set_probes' */
     int64_t nv;                /* width of the probe block the library holds (0: none) */
+    int64_t pnv;               /* width of the precision-probe block the library holds */
 } slot;
 static slot S[NSLOT];          /* handles live across calls */
 
@@ -126,7 +133,7 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
             mexErrMsgIdAndTxt("dcfm:create", "%s", dcfm_last_error(NULL));
         }
         S[i].n = c.n; S[i].P = c.P; S[i].g = c.g; S[i].K = c.K;
-        S[i].mcmc = c.mcmc; S[i].thin = c.thin; S[i].nv = 0;
+        S[i].mcmc = c.mcmc; S[i].thin = c.thin; S[i].nv = 0; S[i].pnv = 0;
         mexLock();
         plhs[0] = mxCreateDoubleScalar(i);
     } else if (!strcmp(cmd, "set_data")) {
@@ -382,6 +389,40 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         const mwSize nv = (mwSize)(cnt > 0 ? t->nv : 0), dq[3] = {nv, nv, (mwSize)cnt};
         plhs[0] = mxCreateNumericArray(3, dq, mxDOUBLE_CLASS, mxREAL);   /* the size the library writes */
         if (cnt > 0) ck(t->h, dcfm_get_probe_draws(t->h, mxGetDoubles(plhs[0]), &cnt));
+    } else if (!strcmp(cmd, "set_precision_probes")) {   /* dcfm_mex('set_precision_probes', h, V[, capacity]) */
+        if (nrhs != 3 && nrhs != 4)
+            mexErrMsgIdAndTxt("dcfm:nargs", "'%s' takes 2 or 3 arguments, got %d", cmd, nrhs - 1);
+        /* the argument that needs no handle first: a malformed call never reaches the library */
+        const double cap = nrhs > 3 ? scalar(prhs[3], "capacity") : -1;
+        if (nrhs > 3 && (cap < 0 || cap > 9007199254740992.0 || cap != (double)(int64_t)cap))
+            mexErrMsgIdAndTxt("dcfm:arg", "capacity must be a non-negative integer");
+        slot *t = get(prhs[1]);
+        const int64_t p = t->P * t->g;               /* the row count the library reads */
+        const int64_t capacity = nrhs > 3 ? (int64_t)cap : (t->thin > 0 ? t->mcmc / t->thin : 0);
+        const mxArray *V = prhs[2];
+        if (capacity > 0 && (!mxIsDouble(V) || mxIsComplex(V) || (int64_t)mxGetM(V) != p || mxGetN(V) > 32 ||
+                             (int64_t)mxGetNumberOfElements(V) != p * (int64_t)mxGetN(V)))
+            mexErrMsgIdAndTxt("dcfm:arg", "V must be a real double p x nv matrix, p = %lld, 0 <= nv <= 32", (long long)p);
+        if (capacity > 0) {
+            const int32_t nv = (int32_t)mxGetN(V);
+            ck(t->h, dcfm_set_precision_probes(t->h, nv > 0 ? mxGetDoubles(V) : NULL, nv, capacity));
+            t->pnv = nv;
+        } else {
+            ck(t->h, dcfm_set_precision_probes(t->h, NULL, 0, 0));
+            t->pnv = 0;
+        }
+    } else if (!strcmp(cmd, "precision_draws")) {    /* [Q, logdet] = dcfm_mex('precision_draws', h) */
+        nargs(nrhs, 2, cmd);
+        slot *t = get(prhs[1]);
+        int64_t cnt = 0;
+        ck(t->h, dcfm_get_precision_draws(t->h, NULL, NULL, &cnt));
+        const mwSize nv = (mwSize)(cnt > 0 ? t->pnv : 0), dq[3] = {nv, nv, (mwSize)cnt};
+        mxArray *Q = mxCreateNumericArray(3, dq, mxDOUBLE_CLASS, mxREAL);   /* the sizes the library writes */
+        mxArray *ld = mxCreateDoubleMatrix((mwSize)cnt, 1, mxREAL);
+        if (cnt > 0) ck(t->h, dcfm_get_precision_draws(t->h, nv > 0 ? mxGetDoubles(Q) : NULL, mxGetDoubles(ld), &cnt));
+        plhs[0] = Q;
+        if (nlhs > 1) plhs[1] = ld;
+        else mxDestroyArray(ld);
     } else if (!strcmp(cmd, "destroy")) {
         nargs(nrhs, 2, cmd);
         slot *t = get(prhs[1]);

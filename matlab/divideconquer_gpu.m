@@ -1,4 +1,4 @@
-function [Sigmaout, Sigmasd] = divideconquer_gpu(Y, g, k, BURNIN, MCMC, thin, rho, seed)
+function [Sigmaout, Sigmasd, Q, logdet] = divideconquer_gpu(Y, g, k, BURNIN, MCMC, thin, rho, seed, Vprec)
 % DIVIDECONQUER_GPU  Sigmaout = divideconquer_gpu(Y,g,k,BURNIN,MCMC,thin,rho[,seed])
 % Same arguments and output as divideconquer.m:1 (posterior-mean covariance in the
 % permuted, standardised coordinates, quirk Q7), with the driver (dc:29-87) and the loop
@@ -11,7 +11,11 @@ function [Sigmaout, Sigmasd] = divideconquer_gpu(Y, g, k, BURNIN, MCMC, thin, rh
 % [Sigmaout, Sigmasd] = divideconquer_gpu(...) also returns the posterior standard deviation
 % of every entry of Sigma over the saved samples (same coordinates): the second moment of the
 % per-sample covariance is accumulated on the GPU beside the mean (cfg.sigma_m2).
-if nargin < 8, seed = 0; end
+% [Sigmaout, Sigmasd, Q, logdet] = divideconquer_gpu(..., seed, Vprec) with Vprec p0 x nv (nv <= 32, one row
+% per column of Y) also records Q(:,:,s) = V' * inv(Sigma_s) * V and logdet(s) = log(det(Sigma_s)) at every saved
+% sample (set_precision_probes), V = Vprec(keepcols(varind), :) the block in Sigmaout's coordinates.
+if nargin < 8 || isempty(seed), seed = 0; end
+if nargin < 9, Vprec = []; end
 [n, p0] = size(Y);
 keepcols = find(arrayfun(@(j) nnz(Y(:, j)), 1:p0) > 0);   % dc:31-38
 p = numel(keepcols);
@@ -27,7 +31,9 @@ h = dcfm_mex('create', cfg);
 cleanup = onCleanup(@() dcfm_mex('destroy', h));
 dcfm_mex('set_data_raw', h, Y, int64(keepcols(varind) - 1));  % dc:48-59 on the device
 dcfm_mex('init_state', h);                                     % dc:68-87 on the device
+if ~isempty(Vprec), dcfm_mex('set_precision_probes', h, Vprec(keepcols(varind), :)); end
 dcfm_mex('run', h, 1, BURNIN + MCMC);                          % dc:90-197
 Sigmaout = dcfm_mex('get_sigma', h, p);
 if nargout > 1, Sigmasd = dcfm_mex('sigma_moment', h, 'sd'); end
+if nargout > 2, [Q, logdet] = dcfm_mex('precision_draws', h); end
 end

@@ -120,7 +120,8 @@ __device__ __forceinline__ double rsqrt_f64(double x) {
 
 // 1/sqrt(x): hardware estimate + one third-order (Halley-type) step y (1 + e/2 + 3e^2/8), e = 1 - x y^2
 // (6 operations instead of rsqrt_f64's 9).  Measured on gfx950 (tools/dev/rsq_acc.hip, 4M arguments over
-// 2^-100 .. 2^100): max relative error 0.624 x 2^-52, as rsqrt_f64 (0.622); the estimate alone 2^-24.2
+// 2^-100 .. 2^100): max relative error 0.624 x 2^-52, as rsqrt_f64 (0.622); the estimate alone 2^-24.2.
+// At the mantissa edges (1 +- ulp, 2^k +- ulp; tests/test_gpu_kunit_wave.py) 0.750 x 2^-52, rsqrt_f64 0.621
 __device__ __forceinline__ double rsqrt_f64_h(double x) {
     const double y = __builtin_amdgcn_rsq(x);
     const double e = fma(-x * y, y, 1.0);
@@ -383,7 +384,8 @@ __device__ __forceinline__ void chol_inv16_p(const double *Sm, int o, double *Ub
     }
 }
 // U = L^{-1} (L L' = S) of a 16x16 SPD tile held in registers in the fp64 MFMA C/D layout (lane
-// (c16, q) holds S[q + 4g][c16] in element g; its upper triangle is read), returned in the same
+// (c16, q) holds S[q + 4g][c16] in element g; its upper triangle is read: the strict lower one enters only
+// products whose results are dropped, so it may hold anything, NaN included), returned in the same
 // layout, by 4 x 4 blocks with no LDS: block step b reads S_bb (10 readlanes), factors it and
 // forms M_b = L_bb^{-1} uniformly in every lane, then four fp64 MFMAs:
 //   P   = S_{.b} M_b'      panel L_{.b}       (A = M_b, B = block row b of S: element b, as held)

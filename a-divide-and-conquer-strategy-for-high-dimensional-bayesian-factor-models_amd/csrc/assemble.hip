@@ -11,6 +11,8 @@ namespace dcfm {
 // ============================================================================
 // saved samples: Lb[(mg*P + j)][slot*K + k] = Lambda, wsum += omega         dc:180-186
 // M2 (DCFM_FLAG_SIGMA_M2): also the sample's own omega, wslot[(mg*P + j)][slot] of B slots
+// K > 32, and K <= 32 with DCFM_FLAG_EXACT_RESIDUAL (omega rewritten after k_lambda); otherwise k_lambda
+// writes the same values itself (SaveArgs, lambda.h) and this launch does not run
 // ============================================================================
 template <bool M2>
 __global__ __launch_bounds__(256) void k_save(Dims d, const double *__restrict__ Lam,

@@ -439,17 +439,47 @@ static void iteration_done(dcfm_handle *h) {
     }
 }
 
-// the loading rows (k_lambda) and dc:169's direct residual where it is asked for
-static void loading_rows(dcfm_handle *h, const DrawsDev &dr, int64_t it, bool lamgen) {
+// dc:180: is iteration it's sample saved?
+static bool saved_iteration(const dcfm_handle *h, int64_t it) { return it % h->cfg.thin == 0 && it > h->cfg.burnin; }
+
+// Who saves it: k_lambda itself (K <= 32: the row's Lambda and omega are in its registers), unless omega is
+// rewritten after it (DCFM_FLAG_EXACT_RESIDUAL: k_resid); then, and for K > 32, k_save copies Lam and omega
+#ifndef DCFM_LAM_SAVE
+#define DCFM_LAM_SAVE 1   // 0: the A/B baseline, k_save always
+#endif
+static bool lambda_saves(const dcfm_handle *h) {
+    return DCFM_LAM_SAVE && h->d.kp == KP && !(h->cfg.flags & DCFM_FLAG_EXACT_RESIDUAL);
+}
+
+// before the first writer of a sample into the open batch: a buffer that is still being assembled
+static int open_batch(dcfm_handle *h) {
+    if (h->batch == 0 && h->asm_pending[h->lb]) {
+        HIPC(h, hipStreamWaitEvent(h->stream, h->e_free[h->lb], 0));
+        h->asm_pending[h->lb] = false;
+    }
+    return DCFM_OK;
+}
+
+// the loading rows (k_lambda) and dc:169's direct residual where it is asked for.  Launch chain of a
+// saved iteration, K <= 32: [wait e_free of a batch's first sample] k_lambda (writes the sample into
+// slot h->batch of Lb / wsum / wslot [h->lb]) -> save_sample: probes, the batch count, the flush of a full
+// batch behind it.  Exact residual and K > 32: k_lambda, k_resid / k_resid_flagged, then k_save.
+static int loading_rows(dcfm_handle *h, const DrawsDev &dr, int64_t it, bool lamgen) {
     const Dims &d = h->d;
     const Bufs &b = h->b;
     hipStream_t s = h->stream;
     // exact residual: k_resid redoes every row below (the guard need not fire); GUARD_ALL: it rejects every row
     const bool exact = h->cfg.flags & DCFM_FLAG_EXACT_RESIDUAL;
     const double kappa_max = exact ? HUGE_VAL : (h->cfg.flags & DCFM_FLAG_GUARD_ALL) ? 0.0 : KAPPA_IDENTITY_MAX;
+    SaveArgs sv;
+    if (lambda_saves(h) && saved_iteration(h, it)) {
+        TRY(open_batch(h));
+        sv.Lb = b.Lb[h->lb]; sv.wsum = b.wsum[h->lb]; sv.wslot = b.wslot[h->lb];
+        sv.LDB = b.LDB; sv.slot = h->batch; sv.B = h->B;
+    }
     {
         KTimer t(h, DCFM_K_LAMBDA, s);
-        launch_lambda(d, b, dr, it, delta_tau(h).tau_in, h->plam_valid ? b.Plam : nullptr, s, lamgen, kappa_max);
+        launch_lambda(d, b, dr, it, delta_tau(h).tau_in, h->plam_valid ? b.Plam : nullptr, s, lamgen, kappa_max, sv);
     }
     if (exact) {                                      // dc:169's residual for every loading row
         KTimer t(h, DCFM_K_RESID, s);
@@ -459,20 +489,20 @@ static void loading_rows(dcfm_handle *h, const DrawsDev &dr, int64_t it, bool la
         launch_resid_flagged(d, b, dr, it, s);
     }
     h->plam_valid = false;
+    return DCFM_OK;
 }
 
-// dc:180: save iteration it's sample into the open assembly batch, handing a full one over
+// dc:180: iteration it's sample is in the open assembly batch (k_lambda wrote it) or goes there now
+// (k_save); a full batch is handed over
 static int save_sample(dcfm_handle *h, int64_t it) {
-    if (it % h->cfg.thin != 0 || it <= h->cfg.burnin) return DCFM_OK;
+    if (!saved_iteration(h, it)) return DCFM_OK;
     const Bufs &b = h->b;
     hipStream_t s = h->stream;
-    if (h->batch == 0 && h->asm_pending[h->lb]) {                 // buffer still being assembled
-        HIPC(h, hipStreamWaitEvent(s, h->e_free[h->lb], 0));
-        h->asm_pending[h->lb] = false;
-    }
-    {
+    const bool ksave = !lambda_saves(h);
+    if (ksave) TRY(open_batch(h));
+    if (ksave || h->probe_n < h->probe_cap || h->prec_n < h->prec_cap) {
         KTimer t(h, DCFM_K_SAVE, s);
-        launch_save(h->d, b, b.Lb[h->lb], b.wsum[h->lb], h->batch, s, b.wslot[h->lb], h->B);
+        if (ksave) launch_save(h->d, b, b.Lb[h->lb], b.wsum[h->lb], h->batch, s, b.wslot[h->lb], h->B);
         if (h->probe_n < h->probe_cap) launch_probes(h->d, b, h->probes, h->probe_n++, s);   // dcfm_set_probes
         if (h->prec_n < h->prec_cap) launch_precision(h->d, b, h->prec, h->prec_n++, s);   // dcfm_set_precision_probes
     }
@@ -490,6 +520,9 @@ static int save_sample(dcfm_handle *h, int64_t it) {
 // delta chain of t-1.  Generated draws (Philox, counter-addressed) are drawn where they are consumed
 // (Z / X normals, the delta gammas) or in the launch before (k_lambda's normals and gammas: the
 // LAMGEN blocks of k_wcol, behind its W tiles).
+// The chain of iteration t:  k_wcol -> [k_xred, all-gather] -> k_xdraw -> k_cpass (+ delta of t - 1) ->
+// k_lambda, which on a saved iteration also writes the sample into the open assembly batch (loading_rows);
+// save_sample then only counts it, launches the probes and hands a full batch to the assembly stream.
 struct FusedSchedule {
     dcfm_handle *h;
     const Dims &d;
@@ -522,7 +555,7 @@ struct FusedSchedule {
         }
         HIPC(h, hipGetLastError());
         if (delta_pending) iteration_done(h);   // outside the timer: it may launch k_trace_part
-        loading_rows(h, dr, it, lamgen);
+        TRY(loading_rows(h, dr, it, lamgen));
         delta_pending = true;     // column sums + delta chain ride in the next iteration's launches
         return DCFM_OK;
     }
@@ -641,7 +674,7 @@ struct SideSchedule {
         HIPC(h, hipStreamWaitEvent(s, h->e_xchol, 0));
         { KTimer t(h, DCFM_K_XDRAW, s); launch_xdraw(d, b, dr, it, s, false); }
         { KTimer t(h, DCFM_K_CPASS, s); launch_cpass(d, b, s); }
-        loading_rows(h, dr, it, false);
+        TRY(loading_rows(h, dr, it, false));
         HIPC(h, hipEventRecord(h->e_lam, s));   // Lambda/omega of this iteration are final
         { KTimer t(h, DCFM_K_COLSUM, s); launch_colsum(d, b, s); }
         if (d.coll) {

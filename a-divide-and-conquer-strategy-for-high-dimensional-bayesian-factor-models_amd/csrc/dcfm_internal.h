@@ -84,6 +84,13 @@ struct DrawsDev {
 // loading-row variates of one iteration in k_lambda's layout (local shard m, loading row j):
 // NL [G][P][K] (dc:142 zlam), Gpsi [G][P][K] (dc:150), Gps [G][P] (dc:170)
 struct LamDraws { const double *NL, *Gpsi, *Gps; };
+// dc:180-186 inside k_lambda (K <= 32): where this iteration's sample goes — row a = (shard0 + m) P + j
+// of the open batch, Lb[a LDB + slot K + k] = Lambda, wsum[a] += omega, wslot[a B + slot] = omega
+// (DCFM_FLAG_SIGMA_M2, else null).  Lb = null: the iteration is not saved, or k_save saves it
+struct SaveArgs {
+    double *Lb = nullptr, *wsum = nullptr, *wslot = nullptr;
+    int LDB = 0, slot = 0, B = 0;
+};
 // k_wcol's extra blocks generate them for the generated fused chain (K <= 32): one index
 // space — [0, n_ps) ps gammas, [n_ps, n_psi) psi gammas, [n_psi, n_all) normal pairs — walked
 // grid-stride by b_total blocks of LAM_GEN_THREADS behind the W tiles (VALU work in the slots
@@ -252,9 +259,11 @@ void launch_cpass(const Dims &d, const Bufs &b, hipStream_t s, const DrawsDev &d
                   double *tau_out = nullptr, int64_t delta_iter = 0);
 // gen: lam_draws_at.  kappa_max: a row whose SS identity may be off by more than ~kappa_max eps (the
 // guard, resid.h) takes ps, omega from dc:169's direct residual instead: K <= 32 its wave's 8 rows in
-// the same launch, K > 32 its 32-row tile in launch_resid_flagged
+// the same launch, K > 32 its 32-row tile in launch_resid_flagged.  sv (K <= 32 only): the kernel also
+// saves the sample
 void launch_lambda(const Dims &d, const Bufs &b, const DrawsDev &dr, int64_t iter,
-                   const double *tau_cur, const double *plam_src, hipStream_t s, bool gen, double kappa_max);
+                   const double *tau_cur, const double *plam_src, hipStream_t s, bool gen, double kappa_max,
+                   const SaveArgs &sv = SaveArgs{});
 void launch_colsum(const Dims &d, const Bufs &b, hipStream_t s);
 // resid.hip (DCFM_FLAG_EXACT_RESIDUAL): ps, omega from the direct residual Yd - eta Lambda' (dc:169-171)
 // for every loading row, after the loading-row kernel, with its ps variates (gen: b.ldraw, else dr)

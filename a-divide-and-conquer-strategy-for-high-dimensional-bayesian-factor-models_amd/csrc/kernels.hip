@@ -140,8 +140,16 @@ __device__ __forceinline__ void xdraw_chunks(int nsrc, int &nch, int &chunk) {
 // source chunk: the shard-message sums are bound by the memory parallelism of the CUs that
 // issue them (phase stamps: 9 of 14 us with 63 blocks of 16 rows at c3).
 constexpr int XD_ROWS = 4;
-constexpr int XD_SMEM = (2 * KP * (KP + 1) + 4 * 4 * 64 * 2) > XCHOL_SMEM ? (2 * KP * (KP + 1) + 4 * 4 * 64 * 2)
-                                                                          : XCHOL_SMEM;
+// Generated X normals (dc:126): wave t < 4 draws Philox pair 4t + q of row i0 + c — one normal2 per
+// wave, between the issue of its message loads and their first use — and hands it to wave 0 through
+// LDS (evs).  Drawn by wave 0 alone, the four pairs ran ahead of its loads, ~1,200 VALU instructions
+// that the other 15 waves waited out at the barrier.  Same counters, formulas and masking.
+#ifndef DCFM_XD_SPREAD
+#define DCFM_XD_SPREAD 1
+#endif
+constexpr bool XD_SPREAD = DCFM_XD_SPREAD;   // 0: the A/B baseline, wave 0 draws the four pairs first
+constexpr int XD_LDS = 2 * KP * (KP + 1) + 4 * 4 * 64 * 2 + 4 * 64 * 2;   // Ms | part | evs
+constexpr int XD_SMEM = XD_LDS > XCHOL_SMEM ? XD_LDS : XCHOL_SMEM;
 __global__ __launch_bounds__(1024) void k_xdraw(Dims d, const double *__restrict__ src, int nsrc, size_t sstride,
                                                 double *__restrict__ XM,
                                                 double *__restrict__ X, DrawsDev dr, int64_t iter, int xroles,
@@ -162,6 +170,7 @@ __global__ __launch_bounds__(1024) void k_xdraw(Dims d, const double *__restrict
     }
     double (*Ms)[KP][KP + 1] = reinterpret_cast<double (*)[KP][KP + 1]>(smem);
     d2 (*part)[4][64] = reinterpret_cast<d2 (*)[4][64]>(smem + 2 * KP * (KP + 1));
+    d2 (*evs)[64] = reinterpret_cast<d2 (*)[64]>(smem + 2 * KP * (KP + 1) + 4 * 4 * 64 * 2);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, c = lane & 15, q = lane >> 4;
     const int tw = w & 3, sw = w >> 2;                 // column group, source chunk
     const int i0 = blk * XD_ROWS, i = i0 + c;
@@ -178,7 +187,7 @@ __global__ __launch_bounds__(1024) void k_xdraw(Dims d, const double *__restrict
             ev[t].x = (live && kk < d.K) ? nx[kk] : 0.0;
             ev[t].y = (live && kk + 1 < d.K) ? nx[kk + 1] : 0.0;
         }
-    } else if (w == 0) {        // generated here (SITE_X, row i): Philox pair 4t + q
+    } else if (w == 0 && !XD_SPREAD) {   // generated here (SITE_X, row i): Philox pair 4t + q
         const Rng rng(d.seed);
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
@@ -196,6 +205,14 @@ __global__ __launch_bounds__(1024) void k_xdraw(Dims d, const double *__restrict
 #pragma unroll
         for (int u = 0; u < 2; ++u) xmv[u] = XM[threadIdx.x + 1024 * u];
     }
+    // wave t = w < 4 (sw = 0 < nch: it has loads below): its pair of the generated normals, ev[t] of wave 0
+    auto draw = [&] {
+        if (!XD_SPREAD || d.inject || w >= 4) return;
+        const int kk = 8 * w + 2 * q;
+        double n0 = 0.0, n1 = 0.0;
+        if (live && kk < d.K) Rng(d.seed).normal2(SITE_X, 0u, (uint32_t)i, (uint32_t)(4 * w + q), (uint32_t)iter, n0, n1);
+        evs[w][lane] = d2{n0, (kk + 1 < d.K) ? n1 : 0.0};
+    };
     if (sw < nch) {
         if (chunk >= 2) {   // lane c sums part c / XD_ROWS (a canonical subtree) of the chunk for row c % XD_ROWS
             // the parts split only a power-of-two chunk (np | chunk, each part a canonical
@@ -207,8 +224,11 @@ __global__ __launch_bounds__(1024) void k_xdraw(Dims d, const double *__restrict
             const bool rl = i0 + rr < d.n && h < np;
             const double *p = src + (size_t)(sw * chunk + (h < np ? h : 0) * per) * stride +
                               (size_t)(i0 + rr < d.n ? i0 + rr : i0) * KP + 8 * tw + 2 * q;
-            d2 v = rl ? tree_sum_f<d2, 8, 10>(per, [&](int rk) { return *reinterpret_cast<const d2 *>(p + (size_t)rk * stride); })
-                      : d2{0.0, 0.0};
+            // a lane with no part sums zeros (the trip counts stay wave-uniform); the draw sits behind the
+            // first batch's loads
+            d2 v = tree_sum_f<d2, 8, 10>(per, [&](int rk) {
+                return rl ? *reinterpret_cast<const d2 *>(p + (size_t)rk * stride) : d2{0.0, 0.0};
+            }, draw);
             for (int o = 1; o < np; o <<= 1) {   // adjacent parts pairwise: the canonical tree over the parts
                 d2 u;
                 u.x = __shfl_down(v.x, o * XD_ROWS, 16);
@@ -219,7 +239,9 @@ __global__ __launch_bounds__(1024) void k_xdraw(Dims d, const double *__restrict
             part[sw][tw][lane] = h == 0 ? v : d2{0.0, 0.0};
         } else {
             const double *p = src + (size_t)sw * chunk * stride + (size_t)(live ? i : i0) * KP + 8 * tw + 2 * q;
-            part[sw][tw][lane] = live ? *reinterpret_cast<const d2 *>(p) : d2{0.0, 0.0};
+            const d2 v = live ? *reinterpret_cast<const d2 *>(p) : d2{0.0, 0.0};
+            draw();
+            part[sw][tw][lane] = v;
         }
     }
     if (xroles & 1) {
@@ -235,6 +257,10 @@ __global__ __launch_bounds__(1024) void k_xdraw(Dims d, const double *__restrict
     }
     __syncthreads();
     if (w > 0) return;
+    if (XD_SPREAD && !d.inject) {
+#pragma unroll
+        for (int t = 0; t < 4; ++t) ev[t] = evs[t][lane];
+    }
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
         TreeSum<d2, 3> ts;
@@ -685,13 +711,14 @@ void launch_cpass(const Dims &d, const Bufs &b, hipStream_t s, const DrawsDev &d
     }
 }
 void launch_lambda(const Dims &d, const Bufs &b, const DrawsDev &dr, int64_t iter,
-                   const double *tau_cur, const double *plam_src, hipStream_t s, bool gen, double kappa_max) {
-    if (d.kp != KP) return wide::launch_lambda(d, b, dr, iter, tau_cur, plam_src, s, kappa_max);
+                   const double *tau_cur, const double *plam_src, hipStream_t s, bool gen, double kappa_max,
+                   const SaveArgs &sv) {
+    if (d.kp != KP) return wide::launch_lambda(d, b, dr, iter, tau_cur, plam_src, s, kappa_max);   // k_save saves
     const LamDraws ld = lam_draws_at(d, b, dr, iter, gen);
     const dim3 grid(cdiv(d.P, LAM_ROWS), d.G);
 #define LAUNCH_LAM(KE)                                                                                       \
     hipLaunchKernelGGL(k_lambda<KE>, grid, dim3(64), 0, s, d, b.C, b.E, b.yy, tau_cur, b.Lam, b.psi, plam_src, \
-                       b.ps, b.omega, b.cpart, ld, b.Y, b.X, b.Z, kappa_max)
+                       b.ps, b.omega, b.cpart, ld, b.Y, b.X, b.Z, kappa_max, sv)
     // the factor width rounded up to an instantiated one (rows >= K are identity padding)
     if (d.K <= 8) LAUNCH_LAM(8);
     else if (d.K <= 16) LAUNCH_LAM(16);

@@ -107,6 +107,9 @@ __device__ __forceinline__ void lam_draws(const Dims &d, const LamGen &lg, int64
 // plam_src is given (first iteration after dcfm_set_state).  The row's variates (dc:142, 150,
 // 170) come from a draw buffer: the generated chain's k_wcol draws them (lam_draws),
 // injected draws and the k_draws batches are read in place.
+// On a saved iteration (sv.Lb, dc:180-186) the wave also writes its rows' sample into the open assembly
+// batch — Lambda_j beside its Lam store, omega_j where it is produced (ps_omega_store) — so no k_save
+// launch re-reads Lam and omega; the same values at the same places, each row's wsum by its one writer.
 // ============================================================================
 // DPP moves within the aligned 8-lane group (every source lane of these patterns is valid)
 template <int CTRL>
@@ -153,7 +156,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_
                                                double *__restrict__ omega, double *__restrict__ cpart,
                                                LamDraws ld, const double *__restrict__ Y,
                                                const double *__restrict__ X, const double *__restrict__ Z,
-                                               double kappa_max) {
+                                               double kappa_max, SaveArgs sv) {
     static_assert(KE % 2 == 0 && KE >= 2 && KE <= KP, "even factor width");
     constexpr int NB = (KE + 7) / 8;
     // LDS: double-buffered image [2][8 systems][KP + 1 (bank spread)][2] | rhs image [2][8][KP+2] |
@@ -453,6 +456,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_
             cpart[rowoff + r] = ps_b * (x[b] * x[b]);               // mat = psijh .* Lambda.^2 (dc:156)
             if (rv[b]) psi[rowoff + r] = ps_b;
         }
+        if (sv.Lb) {   // a saved iteration (dc:180-184): the row into its slot of the open batch, columns < K
+            double *Lr = sv.Lb + ((size_t)mg * d.P + j) * sv.LDB + (size_t)sv.slot * d.K;
+#pragma unroll
+            for (int b = 0; b < 4; ++b)
+                if (rv[b]) Lr[l + 8 * b] = x[b];
+        }
     }
     if (exact) {   // dc:169 as written for the wave's rows: Ytil = Yd - eta Lambda', sum(Ytil.^2)
         double(*Lm)[KP + 1] = reinterpret_cast<double(*)[KP + 1]>(SM);   // the image area, free now
@@ -461,9 +470,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_
         __builtin_amdgcn_wave_barrier();
         const int cc = lane & 15;
         const double gps_c = ld.Gps[(uint32_t)(m * d.P) + (j0 + cc < d.P && cc < LAM_ROWS ? j0 + cc : 0)];
-        resid_rows8(d, Y, X, Z, Lm, gps_c, m, j0, lane, ps, omega);
+        resid_rows8(d, Y, X, Z, Lm, gps_c, m, j0, lane, ps, omega, sv);
     } else if (valid && l == 0) {
-        ps_omega_store(d, SS, Gps, ps, omega, (uint32_t)(m * d.PP + j));
+        ps_omega_store(d, SS, Gps, ps, omega, (uint32_t)(m * d.PP + j), sv, (size_t)mg * d.P + j);
     }
 }
 

@@ -92,6 +92,19 @@ struct TreeSum {
 };
 // sum_{k < n} load(k) in the canonical tree order; the loads go out in batches of B
 // (predicated, all in flight together) before the batch is pushed
+// mid() runs once (n = 0 included), between the first batch's loads and its pushes: work that does not
+// depend on the sum, hidden behind the loads' latency
+template <class T, int B = 8, int L = TREE_LEVELS, class F, class Mid>
+__device__ __forceinline__ T tree_sum_f(int n, F &&load, Mid &&mid) {
+    TreeSum<T, L> ts;
+    for (int k = 0; k == 0 || k < n; k += B) {
+        T v[B];
+        static_for<B>([&](auto U) { if (k + U < n) v[U] = load(k + U); });
+        if (k == 0) mid();
+        static_for<B>([&](auto U) { if (k + U < n) ts.push(v[U]); });
+    }
+    return ts.total();
+}
 template <class T, int B = 8, int L = TREE_LEVELS, class F>
 __device__ __forceinline__ T tree_sum_f(int n, F &&load) {
     TreeSum<T, L> ts;

@@ -15,7 +15,7 @@
 //   V' Sigma(s)^{-1} V = q - rho F' S^{-1} F,      log det Sigma(s) = sum_m ld_m + log det S.
 // B_m and S keep the identity unscaled, so rho = 0 and rho = 1 need no special case.
 //
-// k_precision runs behind k_save (and k_probes) on the sweep stream, slices x G blocks:
+// k_precision runs behind the sample save (and k_probes) on the sweep stream, slices x G blocks:
 //   1. every block reduces a fixed slice of a shard's rows into the lower 16x16 tiles of the weighted Gram
 //      with v_mfma_f64_16x16x4 (the rows staged in LDS 32 at a time, [L | V] padded to 16 columns with
 //      zeros; a wave holds every fourth tile, at most 14, in accumulators) and sum log omega;

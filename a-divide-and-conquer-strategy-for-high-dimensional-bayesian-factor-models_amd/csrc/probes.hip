@@ -2,13 +2,14 @@
 // (dcfm_set_probes / dcfm_get_probe_draws).
 //
 // The reference keeps only the running mean of Sigma (dc:180-196): the per-sample matrix exists for the
-// instant in which k_save copies Lambda and omega into the assembly batch.  Any functional of Sigma that
+// instant in which the sample's Lambda and omega go into the assembly batch (k_lambda itself, K <= 32; else
+// k_save).  Any functional of Sigma that
 // is not one entry -- a portfolio variance v' Sigma v, a correlation, a ratio of variances, a credible
 // interval -- needs its value per saved sample, and none needs Sigma(s) formed.  With L_m the P x K
 // loadings of shard m, V_m the rows of V of that shard and W_m = L_m' V_m (K x nv), W = sum_m W_m,
 //   Sigma(s)     = rho L L' + (1 - rho) blockdiag(L_m L_m') + diag(omega)                     (dc:182-192)
 //   V' Sigma(s) V = rho W' W + sum_m [ (1 - rho) W_m' W_m + V_m' diag(omega_m) V_m ]
-// k_probes runs behind k_save on the sweep stream: slices x G blocks (probe_slices), each reducing a
+// k_probes runs behind the sample save on the sweep stream: slices x G blocks (probe_slices), each reducing a
 // fixed slice of a shard's loading rows into a partial [W (K x nv) | V' Omega V (nv x nv)]; the last
 // slice block of a shard (handoff.h's ticket) adds the slices in slice order and forms the shard's
 // term [W_m | D_m = (1 - rho) W_m' W_m + V_m' Omega_m V_m]; the last shard block of a group of PROBE_FAN

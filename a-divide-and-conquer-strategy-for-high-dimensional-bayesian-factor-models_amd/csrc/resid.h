@@ -22,6 +22,20 @@ __device__ __forceinline__ void ps_omega_store(const Dims &d, double SS, double 
     ps[at] = psn;
     omega[at] = 1.0 / psn;
 }
+// the same with the sample save of dc:185-186 (k_lambda on a saved iteration): the omega just stored
+// goes into row a of the open assembly batch, what k_save would read back and add.  The row's one
+// writer of omega is its one writer of wsum[a], once per sample
+__device__ __forceinline__ void ps_omega_store(const Dims &d, double SS, double Gps, double *ps, double *omega,
+                                               size_t at, const SaveArgs &sv, size_t a) {
+    const double psn = (1.0 / (d.bs + 0.5 * SS)) * Gps;
+    const double w = 1.0 / psn;
+    ps[at] = psn;
+    omega[at] = w;
+    if (sv.Lb) {
+        sv.wsum[a] += w;
+        if (sv.wslot) sv.wslot[a * sv.B + sv.slot] = w;
+    }
+}
 
 // ---- guard of the SS identity.  The loading-row kernels form SS_j = yy_j - 2 lambda_j.C_j + lambda_j E
 //      lambda_j' without a Y pass; its rounding error is ~ kappa_j eps, kappa_j = (the magnitudes it sums) /
@@ -91,12 +105,13 @@ __device__ __forceinline__ void resid_lanesum(double (&ss)[NH]) {
 }
 
 // K <= 32, inside k_lambda: the wave's 8 loading rows j0 .. j0+7 over every chunk of i.  B = the rows'
-// Lambda from k_lambda's LDS image Lm (columns 8..15 of the tile zero), Gps_c the variate of row j0 + c
+// Lambda from k_lambda's LDS image Lm (columns 8..15 of the tile zero), Gps_c the variate of row j0 + c;
+// sv: the omega half of the sample save on a saved iteration (ps_omega_store)
 constexpr int LAM_ROWS = 8;   // loading rows per wave of k_lambda
 __device__ __forceinline__ void resid_rows8(const Dims &d, const double *__restrict__ Y,
                                             const double *__restrict__ X, const double *__restrict__ Z,
                                             const double (*Lm)[KP + 1], double Gps_c, int m, int j0, int lane,
-                                            double *__restrict__ ps, double *__restrict__ omega) {
+                                            double *__restrict__ ps, double *__restrict__ omega, const SaveArgs &sv) {
     constexpr int NT = KP / 8;
     const int c = lane & 15, q = lane >> 4;
     const bool col = c < LAM_ROWS && j0 + c < d.P;
@@ -119,7 +134,8 @@ __device__ __forceinline__ void resid_rows8(const Dims &d, const double *__restr
         }, lb, i0 + q, d.n, ss);
     }
     resid_lanesum(ss);
-    if (q == 0 && col) ps_omega_store(d, ss[0], Gps_c, ps, omega, (uint32_t)(m * d.PP + j0 + c));
+    if (q == 0 && col)
+        ps_omega_store(d, ss[0], Gps_c, ps, omega, (uint32_t)(m * d.PP + j0 + c), sv, (size_t)(d.shard0 + m) * d.P + j0 + c);
 }
 
 // Loading rows j0 .. j0+31 of shard m by a block of 256 threads = 4 waves, which split the chunks of i;

@@ -17,6 +17,10 @@ constexpr int WP_RING = DCFM_WP_RING;   // W pass register ring depth (chunks)
 // the wide layouts' pass (k_wpass<64 / 128>: 2 waves per SIMD at c4) takes one chunk more in flight
 // (c4: 152 -> 127 us; ab_rg in profiles/r06_ab_summary.txt); the same products in the same order
 constexpr int WP_RING_WIDE = DCFM_WP_RING_WIDE;
+#ifndef DCFM_WP_SKIP_PAD
+#define DCFM_WP_SKIP_PAD 1
+#endif
+constexpr bool WP_SKIP_PAD = DCFM_WP_SKIP_PAD;   // 0: the A/B baseline, every chunk of PP (wpass_acc)
 // ============================================================================
 // W pass: W_m[i][k] = sum_j Y_m[i][j] (w_j Lambda_m[j][k])   fp64 MFMA, Y pass 1
 // one wave = (shard m, 16 MT rows i = MT M-tiles) x 32 k (even / odd k tiles) of
@@ -48,7 +52,14 @@ __device__ __forceinline__ void wpass_acc(const Dims &d, const double *__restric
     for (int a = 0; a < MT; ++a)
 #pragma unroll
         for (int b = 0; b < 2; ++b) acc[a][b] = d4{0.0, 0.0, 0.0, 0.0};
-    const int nch = d.PP >> 3;
+    // The reduction stops at the last chunk that holds a data column, ceil(P / 8), not at PP / 8: Y's
+    // padding columns j >= P are zeros (dcfm_set_data, k_stdize), so every product of a whole padding
+    // chunk is +-0 whatever omega and Lambda hold there, and an accumulator that starts at +0 and only
+    // ever adds is never -0, hence unchanged by adding them (c3: P = 312, PP = 320, chunk 39 of 40).
+    // A last partial chunk stays: its padding columns are those zeros of Y.  No caller reads past the
+    // accumulators (wpass_tile's stores and k_wcol's Z draw take acc alone), so none relies on the
+    // padded chunks.  The residual kernels reduce over the rows i, not over j: nothing to skip there.
+    const int nch = WP_SKIP_PAD ? (d.P + 7) >> 3 : d.PP >> 3;
     d2 y0[R], y1[R], ww[R], l0[R], l1[R];
     auto load = [&](int t, int k) {
         const int j = 8 * t;

@@ -8,7 +8,7 @@ mkdir -p $W/pkg $ROOT/build/ab
 cp -r $ROOT/a-divide-and-conquer-strategy-for-high-dimensional-bayesian-factor-models_amd/csrc $W/pkg/csrc
 cp -r $ROOT/include $W/include
 rm -f $W/pkg/csrc/*.o
-make -C $W/pkg/csrc -j8 OUT=$ROOT/build/ab/libdcfm_$NAME.so \
+make -C $W/pkg/csrc -j8 OUT=$ROOT/build/ab/libdcfm_$NAME.so $ROOT/build/ab/libdcfm_$NAME.so \
   CXXFLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -munsafe-fp-atomics -Wall -Wno-unused-function -I/opt/rocm/include -I$W/include $EXTRA" \
   > $W/build.log 2>&1 || { tail -20 $W/build.log; exit 1; }
 rm -rf $W

@@ -28,6 +28,7 @@ DCFM_FLAG_COMM_SELF = 0x20   # one rank on the collective path with a real 1-ran
 DCFM_FLAG_EXACT_RESIDUAL = 0x10  # ps / omega from the direct residual (dc:169), one more Y pass
 DCFM_FLAG_GUARD_ALL = 0x40       # the SS-identity guard rejects every row (its residual fallback, tests)
 DCFM_FLAG_SIGMA_M2 = 0x80        # accumulate the second moment of the per-sample Sigma (M2 / SD read-out)
+DCFM_FLAG_PRECISION_MEAN = 0x100  # accumulate the posterior mean of the per-sample Sigma^-1 (get_precision_mean)
 # dcfm_get_sigma_moment[_cols]'s `which`
 DCFM_SIGMA_MEAN = 0
 DCFM_SIGMA_M2 = 1
@@ -52,7 +53,7 @@ EXPORTS = (
     "dcfm_rng_fill", "dcfm_rng_fill_rows", "dcfm_set_data_raw", "dcfm_get_data", "dcfm_count_nonzero_columns",
     "dcfm_set_trace", "dcfm_get_trace", "dcfm_init_state", "dcfm_sigma_apply", "dcfm_sigma_eigs",
     "dcfm_sigma_solve", "dcfm_set_probes", "dcfm_get_probe_draws", "dcfm_set_precision_probes",
-    "dcfm_get_precision_draws",
+    "dcfm_get_precision_draws", "dcfm_get_precision_mean_cols", "dcfm_get_precision_mean",
 )
 
 
@@ -121,6 +122,8 @@ def load_library(path: Path | None = None):
         "dcfm_sigma_block": (C.c_int, [vp, C.POINTER(C.c_int64)]),
         "dcfm_get_sigma_moment_cols": (C.c_int, [vp, C.c_int32, C.c_int64, C.c_int64, _DP]),
         "dcfm_get_sigma_moment": (C.c_int, [vp, C.c_int32, _DP]),
+        "dcfm_get_precision_mean_cols": (C.c_int, [vp, C.c_int64, C.c_int64, _DP]),
+        "dcfm_get_precision_mean": (C.c_int, [vp, _DP]),
         "dcfm_saved_samples": (C.c_int64, [vp]),
         "dcfm_sigma_error": (C.c_int, [vp, _DP, C.c_int32, _DP, C.c_int32, C.c_uint64, _DP]),
         "dcfm_sigma_apply": (C.c_int, [vp, _DP, C.c_int32, _DP, _DP]),

@@ -242,6 +242,16 @@ static int alloc_buffers(dcfm_handle *h) {
     TRY(dalloc(h, &b.Sigma, (size_t)(tri(b.T1) - tri(b.T0)) * ASM_TILE * ASM_TILE));
     if (c.flags & DCFM_FLAG_SIGMA_M2) {   // second moment beside the mean, and each saved sample's own omega
         TRY(dalloc(h, &b.Sigma2, (size_t)(tri(b.T1) - tri(b.T0)) * ASM_TILE * ASM_TILE));
+    }
+    if (c.flags & DCFM_FLAG_PRECISION_MEAN) {   // mean of the per-sample inverse, its factor panels and K x K scratch
+        PrecMean &pm = h->pm;
+        TRY(dalloc(h, &pm.Prec, (size_t)(tri(b.T1) - tri(b.T0)) * ASM_TILE * ASM_TILE));
+        pm.KH = round_up(h->B * d.K, ASM_KC);
+        TRY(dalloc(h, &pm.pfac, p * 4 * (size_t)pm.KH));
+        TRY(dalloc(h, &pm.pscr, precision_mean_scratch_doubles(d.g, d.K, h->B)));
+        HIPC(h, precision_mean_setup());
+    }
+    if (c.flags & (DCFM_FLAG_SIGMA_M2 | DCFM_FLAG_PRECISION_MEAN)) {   // each saved sample's own omega
         TRY(dalloc(h, &b.wslot[0], p * (size_t)h->B));
         TRY(dalloc(h, &b.wslot[1], p * (size_t)h->B));
     }
@@ -377,7 +387,7 @@ static int flush_batch(dcfm_handle *h) {
                                 h->sasm);
         if (rc == DCFM_OK)
             rc = coll_allgather(h, CH_ASM, b.wsum[lb] + (size_t)d.rank * rows, b.wsum[lb], rows, h->sasm);
-        if (rc == DCFM_OK && b.Sigma2)
+        if (rc == DCFM_OK && b.wslot[lb])
             rc = coll_allgather(h, CH_ASM, b.wslot[lb] + (size_t)d.rank * rows * h->B, b.wslot[lb], rows * h->B,
                                 h->sasm);
         if (!h->loop) NCCLC(h, ncclGroupEnd());
@@ -397,6 +407,8 @@ static int flush_batch(dcfm_handle *h) {
         launch_assemble(d, b, b.Lb[lb], b.wsum[lb], kext, 1.0 / effsamp, h->sasm);
         // DCFM_FLAG_SIGMA_M2: the batch's samples one by one into the second moment
         if (b.Sigma2) launch_assemble_m2(d, b, b.Lb[lb], b.wslot[lb], h->batch, h->B, 1.0 / effsamp, h->sasm);
+        // DCFM_FLAG_PRECISION_MEAN: the batch's per-sample inverses into the precision mean
+        if (h->pm.Prec) launch_precision_mean(d, b, h->pm, b.Lb[lb], b.wslot[lb], h->batch, h->B, 1.0 / effsamp, h->sasm);
     }
     HIPC(h, hipGetLastError());
     HIPC(h, hipMemsetAsync(b.wsum[lb], 0, (size_t)d.p * sizeof(double), h->sasm));   // k_save adds into it

@@ -23,7 +23,10 @@
 //   sloc   [G][KW], sall [g][KW]  column sums (all-gathered)
 //   Lb     [2][p][LDB]   saved Lambda rows of an assembly batch (double-buffered), sample s at cols s*K..
 //   wsum   [2][p]        sum of saved omega of the batch
-//   wslot  [2][p][B]     DCFM_FLAG_SIGMA_M2: each saved sample's own omega (slot s of row a at a*B + s)
+//   wslot  [2][p][B]     DCFM_FLAG_SIGMA_M2 / _PRECISION_MEAN: each saved sample's own omega (slot s of row a at a*B + s)
+//   Prec   [ntiles][128][128]  DCFM_FLAG_PRECISION_MEAN: mean of the per-sample Sigma^{-1}, laid out as Sigma
+//   pfac   [p][4 KH]     DCFM_FLAG_PRECISION_MEAN: the factor panels of a flush (precision_mean.hip), KH = round_up(B K, 16);
+//                        pscr [(2 g + 1) B][K][K] the shards' H_m, B_m^{-1} and the slots' S^{-1}
 //   Sigma2 [ntiles][128][128]  DCFM_FLAG_SIGMA_M2: second moment of the per-sample Sigma, laid out as Sigma
 //   Sigma  [ntiles][128][128]  this rank's block of the lower triangle of Sigmaout, tile-packed:
 //                        rank r owns the contiguous tile rows [T0, T1) (balanced by tile count,
@@ -120,7 +123,8 @@ struct Bufs {
     double *ldraw;                     // LamDraws of the generated fused chain (lam_gen_plan), else null
     double *W, *A, *ZM, *Sp, *xin, *xall, *C, *E, *cpart, *sloc, *sall;
     double *Lb[2], *wsum[2], *Sigma;
-    double *wslot[2], *Sigma2;         // DCFM_FLAG_SIGMA_M2: per-sample omega of a batch, second moment; else null
+    double *wslot[2], *Sigma2;         // DCFM_FLAG_SIGMA_M2: per-sample omega of a batch (also with _PRECISION_MEAN),
+                                       // second moment; else null
     double *xa, *xa_all, *XM;          // per-rank sum of A, gathered sums, X-draw operators
     double *xpart;                     // k_wcol chunk sums of A (xsum_blocks(G) x KP x KP)
     unsigned *ticket;                  // k_wcol last-arrival ticket (0 between launches)
@@ -189,6 +193,13 @@ struct Precision {
     unsigned *ticket;
     int nv, slices;
     size_t slot, lds;
+};
+// Precision mean (precision_mean.hip, DCFM_FLAG_PRECISION_MEAN; all null when off).  Kept out of Bufs, which
+// the sweep's kernels take by value: Prec the accumulator (laid out as Bufs::Sigma), pfac the factor panels of
+// a flush, pscr the K x K scratch, KH the columns of a quarter of pfac (B K rounded up to ASM_KC)
+struct PrecMean {
+    double *Prec, *pfac, *pscr;
+    int KH;
 };
 // Bufs::sync: [0] the X operators (k_xdraw, several ranks), [1] spare, [2, 2 + 256) chunk counters of the A sum, [SYNC_ZM, SYNC_ZM + G) the
 // per-shard Z-operator counters (the fused W pass draws Z once its shard's operators are out)
@@ -284,6 +295,12 @@ void launch_assemble(const Dims &d, const Bufs &b, const double *Lb, const doubl
 // per-sample Sigma (Lb slots of K columns, wslot [p][B] the samples' omega)
 void launch_assemble_m2(const Dims &d, const Bufs &b, const double *Lb, const double *wslot, int nslots, int B,
                         double inv_eff, hipStream_t s);
+// precision_mean.hip: pm.Prec += (1 / effsamp) sum over the batch's nslots samples of Sigma(s)^{-1}, from the
+// gathered Lb slots and wslot [p][B] of ALL g shards; setup once per process before the first launch
+size_t precision_mean_scratch_doubles(int g, int K, int B);
+hipError_t precision_mean_setup();
+void launch_precision_mean(const Dims &d, const Bufs &b, const PrecMean &pm, const double *Lb, const double *wslot, int nslots, int B,
+                           double inv_eff, hipStream_t s);
 // column stripe [c0, c0 + nc) of Sigmaout from a rank's tile-packed block (tile rows [T0, T1)):
 // the rank's packed windows (win_lo / win_off; with one rank = the dense p x nc stripe).
 // which (DCFM_SIGMA_*): 0 the mean S, 1 the second moment S2, 2 sqrt(max(0, rs S2 - (rs S)^2))

@@ -80,6 +80,8 @@ struct dcfm_handle {
     double *prec_mem = nullptr;
     Precision prec{};
     int64_t prec_cap = 0, prec_n = 0;
+    // posterior mean of the precision matrix (DCFM_FLAG_PRECISION_MEAN, precision_mean.hip): null when off
+    PrecMean pm{};
     bool prof = false;
     uint32_t prof_mask = 0;       // kernel ids (bit DCFM_K_*) timed with events
     int prof_stride = 1;          // time one in prof_stride launches of each (dcfm_set_profiling_stride)

@@ -5,7 +5,8 @@
 // Columns [col0, col0 + ncols) of one posterior moment of Sigma (DCFM_SIGMA_*), gathered to the
 // root rank: the one body of dcfm_get_sigma_cols (the mean) and dcfm_get_sigma_moment_cols.  The
 // moments differ only in what k_sigma_pack reads from the rank's block(s).
-static int sigma_moment_cols(dcfm_handle *h, int which, int64_t col0, int64_t ncols, double *out) {
+// prec: the same read-out pointed at the precision mean (dcfm_get_precision_mean_cols; which = DCFM_SIGMA_MEAN).
+static int sigma_moment_cols(dcfm_handle *h, int which, int64_t col0, int64_t ncols, double *out, bool prec = false) {
     if (!h) return fail(h, DCFM_ERR_INVALID, "null handle");
     Dims &d = h->d;
     const int root = 0;
@@ -13,6 +14,8 @@ static int sigma_moment_cols(dcfm_handle *h, int which, int64_t col0, int64_t nc
     double rs = 1.0;   // SD: effsamp / saved samples (the moments carry 1 / effsamp, quirk Q8)
     if (which != DCFM_SIGMA_MEAN && which != DCFM_SIGMA_M2 && which != DCFM_SIGMA_SD)
         code = fail(h, DCFM_ERR_INVALID, "sigma moment %d: DCFM_SIGMA_MEAN, _M2 or _SD", which);
+    else if (prec && !h->pm.Prec)
+        code = fail(h, DCFM_ERR_INVALID, "the precision mean needs DCFM_FLAG_PRECISION_MEAN at dcfm_create");
     else if (which != DCFM_SIGMA_MEAN && !h->b.Sigma2)
         code = fail(h, DCFM_ERR_INVALID, "the second moment and the standard deviation of Sigma need "
                                          "DCFM_FLAG_SIGMA_M2 at dcfm_create");
@@ -66,7 +69,7 @@ static int sigma_moment_cols(dcfm_handle *h, int which, int64_t col0, int64_t nc
     double *buf = static_cast<double *>(q);
     double *mine = is_root ? buf + base[d.rank] : buf;
     int rc = DCFM_OK;
-    launch_sigma_pack(h->b.Sigma, h->b.Sigma2, which, rs, d.p, h->b.T0, h->b.T1, (int)col0, (int)ncols, mine,
+    launch_sigma_pack(prec ? h->pm.Prec : h->b.Sigma, h->b.Sigma2, which, rs, d.p, h->b.T0, h->b.T1, (int)col0, (int)ncols, mine,
                       h->stream);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) rc = fail(h, DCFM_ERR_HIP, "sigma_pack: %s", hipGetErrorString(e));
@@ -106,13 +109,15 @@ static int sigma_moment_cols(dcfm_handle *h, int which, int64_t col0, int64_t nc
 }
 
 // the whole p x p moment in column stripes of <= 2 GiB
-static int sigma_moment(dcfm_handle *h, int which, double *out) {
+static int sigma_moment(dcfm_handle *h, int which, double *out, bool prec = false) {
     if (!h) return fail(h, DCFM_ERR_INVALID, "null handle");
+    if (prec && !h->pm.Prec)
+        return fail(h, DCFM_ERR_INVALID, "the precision mean needs DCFM_FLAG_PRECISION_MEAN at dcfm_create");
     if (!out && h->d.rank == 0) return fail(h, DCFM_ERR_INVALID, "null output on the root rank");
     const int64_t p = h->d.p;
     const int64_t chunk = std::max<int64_t>(32, std::min<int64_t>(p, ((int64_t)1 << 28) / p));
     for (int64_t c = 0; c < p; c += chunk) {
-        const int rc = sigma_moment_cols(h, which, c, std::min(chunk, p - c), out ? out + (size_t)c * p : nullptr);
+        const int rc = sigma_moment_cols(h, which, c, std::min(chunk, p - c), out ? out + (size_t)c * p : nullptr, prec);
         if (rc) return rc;
     }
     return DCFM_OK;
@@ -132,13 +137,19 @@ int dcfm_get_sigma(dcfm_handle *h, double *out) { return sigma_moment(h, DCFM_SI
 
 int dcfm_get_sigma_moment(dcfm_handle *h, int32_t which, double *out) { return sigma_moment(h, which, out); }
 
+int dcfm_get_precision_mean_cols(dcfm_handle *h, int64_t col0, int64_t ncols, double *out) {
+    return sigma_moment_cols(h, DCFM_SIGMA_MEAN, col0, ncols, out, true);
+}
+
+int dcfm_get_precision_mean(dcfm_handle *h, double *out) { return sigma_moment(h, DCFM_SIGMA_MEAN, out, true); }
+
 int dcfm_sigma_block(const dcfm_handle *h, int64_t out[3]) {
     if (!h || !out) return fail(nullptr, DCFM_ERR_INVALID, "null argument");
     const int64_t p = h->d.p;
     out[0] = std::min<int64_t>(p, (int64_t)h->b.T0 * ASM_TILE);
     out[1] = std::min<int64_t>(p, (int64_t)h->b.T1 * ASM_TILE);
     out[2] = (int64_t)(tri(h->b.T1) - tri(h->b.T0)) * ASM_TILE * ASM_TILE * (int64_t)sizeof(double) *
-             (h->b.Sigma2 ? 2 : 1);   // DCFM_FLAG_SIGMA_M2: the second moment beside the mean
+             (1 + (h->b.Sigma2 ? 1 : 0) + (h->pm.Prec ? 1 : 0));   // the second moment, the precision mean beside the mean
     return DCFM_OK;
 }
 

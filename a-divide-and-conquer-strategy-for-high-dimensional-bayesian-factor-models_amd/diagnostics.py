@@ -126,3 +126,19 @@ def heldout_log_density(Q, logdet, p) -> dict:
     with np.errstate(divide="ignore"):
         lppd = safe + np.log(np.mean(np.exp(per - safe), axis=0))
     return {"per_sample": per, "lppd": lppd, "total": float(lppd.sum())}
+
+
+def partial_correlations(T) -> np.ndarray:
+    """Partial correlations from a precision matrix T (``Sampler.get_precision_mean``, or any symmetric
+    p x p precision): ``-T_ab / sqrt(T_aa T_bb)`` off the diagonal, the correlation of variables a and b
+    given all the others, with a unit diagonal.  NaN in the rows and columns whose diagonal entry is not
+    positive."""
+    T = np.asarray(T, dtype=np.float64)
+    if T.ndim != 2 or T.shape[0] != T.shape[1]:
+        raise ValueError(f"T must be p x p, got {T.shape}")
+    d = T.diagonal()
+    with np.errstate(divide="ignore", invalid="ignore"):
+        s = np.sqrt(np.where(d > 0, d, np.nan))
+        R = -T / (s[:, None] * s[None, :])
+    R[np.diag_indices_from(R)] = np.where(d > 0, 1.0, np.nan)
+    return R

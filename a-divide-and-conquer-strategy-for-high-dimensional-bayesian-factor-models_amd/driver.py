@@ -135,7 +135,7 @@ def local_state(state: dict, s0: int, gl: int) -> dict:
 def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hyper(),
                   init_draws=None, iter_draws=None, nranks=1, rank=0, device=0, comm_uid=None,
                   asm_batch=0, return_info=False, device_ingest=True, device_init=True, return_sd=False,
-                  n_components=0, rhs=None, probes=None, precision_probes=None):
+                  n_components=0, rhs=None, probes=None, precision_probes=None, return_precision=False):
     """Sigmaout = divideconquer(Y,g,k,BURNIN,MCMC,thin,rho)   (divideconquer.m:1).
 
     ``device_ingest`` (default): the zero-column scan and the partition/standardisation
@@ -152,6 +152,12 @@ def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hy
     (DCFM_FLAG_SIGMA_M2) and return ``(Sigmaout, Sigmasd)`` — or ``(Sigmaout, Sigmasd, info)`` with
     ``return_info`` — where Sigmasd is the p x p posterior standard deviation of every entry over
     the saved samples, in Sigmaout's coordinates.
+
+    ``return_precision``: also accumulate the posterior mean of the precision matrix on the device
+    (DCFM_FLAG_PRECISION_MEAN) and append Theta = (1/effsamp) sum_s inv(Sigma(s)) -- p x p, in Sigmaout's
+    coordinates; E[inv(Sigma)], not the inverse of Sigmaout -- to the returned tuple after Sigmasd (if
+    requested) and before the ``n_components`` dict.  ``unpermute_precision`` takes it back to the input's
+    column order and ``diagnostics.partial_correlations`` reads the partial correlations off it.
 
     ``n_components`` > 0: also the leading principal components of Sigmaout, found on the device
     (Sampler.sigma_eigs: ``values``, ``vectors`` p x n_components, ``resid``, ``passes``,
@@ -214,7 +220,7 @@ def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hy
     s0 = rank * gl
     smp = Sampler(n, P, g, K, rho, BURNIN, MCMC, thin, hyper=hyper, seed=seed, nranks=nranks,
                   rank=rank, device=device, inject_draws=iter_draws is not None, asm_batch=asm_batch,
-                  sigma_m2=return_sd)
+                  sigma_m2=return_sd, precision_mean=return_precision)
     try:
         if nranks > 1:
             if comm_uid is None:
@@ -237,6 +243,7 @@ def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hy
         smp.run(1, N)                                            # dc:90-197
         Sigmaout = smp.get_sigma()
         Sigmasd = smp.get_sigma_moment("sd") if return_sd else None
+        Theta = smp.get_precision_mean() if return_precision else None
         pcs = smp.sigma_eigs(int(n_components)) if n_components > 0 else None
         sol = None
         if rhs is not None:
@@ -254,6 +261,8 @@ def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hy
         smp.close()
     elapsed = time.perf_counter() - t0                           # dc:200 toc
     out = (Sigmaout, Sigmasd) if return_sd else (Sigmaout,)
+    if return_precision:
+        out += (Theta,)
     if n_components > 0:
         out += (pcs,)
     if rhs is not None:
@@ -303,6 +312,24 @@ def unpermute_sigma(S, keep, varind, p_orig, sd=None, fill=0.0):
         S = S * sd[:, None] * sd[None, :]
     out = np.full((p_orig, p_orig), fill, dtype=np.float64)
     out[np.ix_(cols, cols)] = S
+    return out
+
+
+def unpermute_precision(T, keep, varind, p_orig, sd=None, fill=0.0):
+    """The precision mean Theta of ``divideconquer(..., return_precision=True)`` back in the input's column
+    order: T[a, b] goes to (cols[a], cols[b]) with cols = output_columns(keep, varind); rows/columns of
+    dropped (all-zero, dc:36-39) columns get ``fill``.  With ``sd`` (the sample standard deviations of the
+    kept columns in Sigmaout's order, dc:57) the standardisation is undone: the unstandardised covariance
+    is D S D with D = diag(sd) and (D S D)^-1 = D^-1 S^-1 D^-1, so the entry is *divided*,
+    T_ab / (sd_a sd_b) -- the inverse of what ``unpermute_sigma`` does, so that the two results stay
+    inverse to each other on the kept block."""
+    T = np.asarray(T, dtype=np.float64)
+    cols = output_columns(keep, varind)
+    if sd is not None:
+        sd = np.asarray(sd, dtype=np.float64)
+        T = T / sd[:, None] / sd[None, :]
+    out = np.full((p_orig, p_orig), fill, dtype=np.float64)
+    out[np.ix_(cols, cols)] = T
     return out
 
 

@@ -40,7 +40,8 @@ class Sampler:
     """One rank's handle: shards [rank*g_local, (rank+1)*g_local) of a chain."""
 
     def __init__(self, n, P, g, K, rho, burnin, mcmc, thin, *, hyper: Hyper = Hyper(), seed=0,
-                 nranks=1, rank=0, device=0, inject_draws=False, asm_batch=0, flags=0, sigma_m2=False):
+                 nranks=1, rank=0, device=0, inject_draws=False, asm_batch=0, flags=0, sigma_m2=False,
+                 precision_mean=False):
         self.lib = _abi.load_library()
         cfg = _abi.DcfmConfig()
         cfg.n, cfg.P, cfg.g, cfg.K = int(n), int(P), int(g), int(K)
@@ -51,7 +52,8 @@ class Sampler:
         cfg.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         cfg.nranks, cfg.rank, cfg.device = int(nranks), int(rank), int(device)
         cfg.flags = ((_abi.DCFM_FLAG_INJECT_DRAWS if inject_draws else 0) |
-                     (_abi.DCFM_FLAG_SIGMA_M2 if sigma_m2 else 0) | int(flags))
+                     (_abi.DCFM_FLAG_SIGMA_M2 if sigma_m2 else 0) |
+                     (_abi.DCFM_FLAG_PRECISION_MEAN if precision_mean else 0) | int(flags))
         cfg.asm_batch = int(asm_batch)
         self.cfg = cfg
         h = C.c_void_p()
@@ -241,8 +243,32 @@ class Sampler:
         self._check(self.lib.dcfm_get_sigma_moment_cols(self.h, w, int(col0), int(ncols), _ptr(S)))
         return S
 
+    def get_precision_mean(self):
+        """The posterior mean of the precision matrix, ``(1/effsamp) sum_s inv(Sigma(s))`` over the saved
+        samples (p x p, Fortran order, Sigmaout's coordinates and 1/effsamp scaling; all zeros before the
+        first saved sample).  E[inv(Sigma)], not ``inv(get_sigma())``.  Needs ``precision_mean=True``.
+        Symmetric bit for bit.  Collective like get_sigma(): rank 0 receives it, the others get None."""
+        p = self.P * self.g
+        if self.rank != 0:
+            self._check(self.lib.dcfm_get_precision_mean(self.h, None))
+            return None
+        T = np.zeros((p, p), dtype=np.float64, order="F")
+        self._check(self.lib.dcfm_get_precision_mean(self.h, _ptr(T)))
+        return T
+
+    def get_precision_mean_cols(self, col0: int, ncols: int):
+        """Columns [col0, col0+ncols) of get_precision_mean(), p x ncols (as get_sigma_cols)."""
+        p = self.P * self.g
+        if self.rank != 0:
+            self._check(self.lib.dcfm_get_precision_mean_cols(self.h, int(col0), int(ncols), None))
+            return None
+        T = np.zeros((p, int(ncols)), dtype=np.float64, order="F")
+        self._check(self.lib.dcfm_get_precision_mean_cols(self.h, int(col0), int(ncols), _ptr(T)))
+        return T
+
     def sigma_block(self) -> dict:
-        """This rank's block of Sigmaout: rows [row0, row1) of the lower triangle and its bytes."""
+        """This rank's block of Sigmaout: rows [row0, row1) of the lower triangle and its bytes
+        (the mean, plus the second moment with ``sigma_m2`` and the precision mean with ``precision_mean``)."""
         out = (C.c_int64 * 3)()
         self._check(self.lib.dcfm_sigma_block(self.h, out))
         return {"row0": int(out[0]), "row1": int(out[1]), "bytes": int(out[2])}

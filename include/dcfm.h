@@ -70,6 +70,12 @@ extern "C" {
                                         Sigmaout block, one more assembly kernel per flush), for
                                         dcfm_get_sigma_moment's M2 and SD; off: nothing is
                                         allocated or launched                              */
+#define DCFM_FLAG_PRECISION_MEAN 0x100u /* also accumulate the posterior mean of the precision matrix,
+                                        (1/effsamp) sum_s Sigma(s)^-1 (one more buffer the size of this
+                                        rank's Sigmaout block, the per-sample omega slots, a factor
+                                        buffer and the kernels of precision_mean.hip per flush), for
+                                        dcfm_get_precision_mean[_cols]; off: nothing is allocated or
+                                        launched                                          */
 
 typedef struct dcfm_handle dcfm_handle;
 
@@ -198,8 +204,9 @@ int  dcfm_get_sigma_cols(dcfm_handle *h, int64_t col0, int64_t ncols, double *ou
 /* This rank's block of Sigmaout (the build's output sharding; the reference holds
  * the whole p x p, dc:42): out[0], out[1] = the rows [row0, row1) whose lower
  * triangle it accumulates (contiguous 128-row tiles, balanced by tile count over
- * the ranks), out[2] = its device bytes for Sigmaout (~p^2 / (2 nranks) * 8; twice that
- * with DCFM_FLAG_SIGMA_M2: the second moment beside the mean). */
+ * the ranks), out[2] = its device bytes for Sigmaout (~p^2 / (2 nranks) * 8; once more
+ * with DCFM_FLAG_SIGMA_M2, the second moment beside the mean, and once more with
+ * DCFM_FLAG_PRECISION_MEAN, the precision accumulator). */
 int  dcfm_sigma_block(const dcfm_handle *h, int64_t out[3]);
 int64_t dcfm_saved_samples(const dcfm_handle *h);
 /* Posterior moments of Sigma's entries.  With Sigma(s) the matrix dc:182-192 builds from saved
@@ -219,6 +226,16 @@ int64_t dcfm_saved_samples(const dcfm_handle *h);
 #define DCFM_SIGMA_SD   2
 int  dcfm_get_sigma_moment_cols(dcfm_handle *h, int32_t which, int64_t col0, int64_t ncols, double *out);
 int  dcfm_get_sigma_moment(dcfm_handle *h, int32_t which, double *out);
+/* Posterior mean of the precision matrix (DCFM_FLAG_PRECISION_MEAN at dcfm_create, else
+ * DCFM_ERR_INVALID): Theta = (1/effsamp) sum_s Sigma(s)^-1 over the saved samples, Sigma(s) the
+ * per-sample matrix of dc:182-192, with the same effsamp = mcmc/thin scaling (quirk Q8) as Sigmaout;
+ * all zeros before the first saved sample.  This is E[Sigma^-1 | Y], not the inverse of the posterior
+ * mean (dcfm_sigma_solve).  Accumulated on the device tile by tile from thin factor panels (Sigma(s)^-1
+ * is block-diagonal plus low rank, as Sigma(s) is): no p x p factorisation.  An entry is accurate to
+ * first order in eps cond(Sigma(s)).  p x p in Sigmaout's coordinates, symmetric bit for bit; layout,
+ * striping and collective semantics as dcfm_get_sigma_cols / dcfm_get_sigma. */
+int  dcfm_get_precision_mean_cols(dcfm_handle *h, int64_t col0, int64_t ncols, double *out);
+int  dcfm_get_precision_mean(dcfm_handle *h, double *out);
 /* Error of Sigmaout against a truth Sigma0 = U U' + diag(s) given in the same permuted,
  * standardised coordinates (U: p x r column-major, r <= 32; s: p), computed on the
  * device (Sigmaout never leaves HBM; c5: 80 GB).  out[0] = ||Sigmaout - Sigma0||_F,

@@ -7,6 +7,7 @@
  * on the GPU).  Commands:
  *   h = dcfm_mex('create', cfg)           cfg fields n P g K rho burnin mcmc thin as bs df ad1
  *                                         bd1 ad2 bd2 seed device inject asm_batch sigma_m2
+ *                                         precision_mean
  *   dcfm_mex('set_data', h, Yd)           Yd n x P x g (dc:49-59 done by the caller)
  *   dcfm_mex('set_data_raw', h, Y0, cols) raw n x p0 data + int64 0-based columns (dc:48-59 on GPU)
  *   dcfm_mex('set_state', h, Lambda, ps, omega, psijh, Plam, X, Z, delta, tauh)
@@ -20,6 +21,10 @@
  *                                         mean, second moment or standard deviation of Sigma's
  *                                         entries ('m2', 'sd' need cfg.sigma_m2 = 1), p x p or
  *                                         the columns col0 .. col0+ncols-1 (0-based), p x ncols
+ *   T = dcfm_mex('precision_mean', h[, col0, ncols])   the posterior mean of the precision matrix,
+ *                                         (1/effsamp) * sum over the saved samples of inv(Sigma_s) (needs
+ *                                         cfg.precision_mean = 1), p x p or the columns col0 .. col0+ncols-1
+ *                                         (0-based), p x ncols; Sigmaout's coordinates
  *   Y = dcfm_mex('sigma_apply', h, V)     Y = Sigmaout * V on the device, V p x nv (any nv >= 1), in
  *                                         Sigmaout's permuted, standardised coordinates
  *   [d, V, res] = dcfm_mex('sigma_eigs', h, r[, tol, max_passes, seed])   the r <= 32 largest eigenpairs
@@ -124,6 +129,7 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         c.seed = (uint64_t)fld(s, "seed", 0); c.nranks = 1; c.device = (int32_t)fld(s, "device", 0);
         c.flags = fld(s, "inject", 0) != 0 ? DCFM_FLAG_INJECT_DRAWS : 0u;
         if (fld(s, "sigma_m2", 0) != 0) c.flags |= DCFM_FLAG_SIGMA_M2;
+        if (fld(s, "precision_mean", 0) != 0) c.flags |= DCFM_FLAG_PRECISION_MEAN;
         c.asm_batch = (int32_t)fld(s, "asm_batch", 0);
         int i = 0;
         while (i < NSLOT && S[i].h) ++i;
@@ -288,6 +294,23 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
             mexErrMsgIdAndTxt("dcfm:arg", "columns [%g, %g) outside 0..p = %lld", c0, c0 + nc, (long long)p);
         plhs[0] = mxCreateDoubleMatrix((mwSize)p, (mwSize)nc, mxREAL);
         ck(t->h, dcfm_get_sigma_moment_cols(t->h, which, (int64_t)c0, (int64_t)nc, mxGetDoubles(plhs[0])));
+    } else if (!strcmp(cmd, "precision_mean")) {     /* T = dcfm_mex('precision_mean', h[, col0, ncols]) */
+        if (nrhs != 2 && nrhs != 4)
+            mexErrMsgIdAndTxt("dcfm:nargs", "'%s' takes 1 or 3 arguments, got %d", cmd, nrhs - 1);
+        double c0 = 0, nc = -1;                      /* checked as 'sigma_moment' checks its range */
+        if (nrhs == 4) {
+            c0 = scalar(prhs[2], "col0");
+            nc = scalar(prhs[3], "ncols");
+            if (c0 < 0 || nc < 0 || c0 != (double)(int64_t)c0 || nc != (double)(int64_t)nc)
+                mexErrMsgIdAndTxt("dcfm:arg", "col0 and ncols must be non-negative integers");
+        }
+        slot *t = get(prhs[1]);
+        const int64_t p = t->P * t->g;               /* the size the library writes */
+        if (nc < 0) nc = (double)p;
+        if (c0 + nc > (double)p)
+            mexErrMsgIdAndTxt("dcfm:arg", "columns [%g, %g) outside 0..p = %lld", c0, c0 + nc, (long long)p);
+        plhs[0] = mxCreateDoubleMatrix((mwSize)p, (mwSize)nc, mxREAL);
+        ck(t->h, dcfm_get_precision_mean_cols(t->h, (int64_t)c0, (int64_t)nc, mxGetDoubles(plhs[0])));
     } else if (!strcmp(cmd, "sigma_apply")) {        /* Y = dcfm_mex('sigma_apply', h, V) */
         nargs(nrhs, 3, cmd);
         slot *t = get(prhs[1]);

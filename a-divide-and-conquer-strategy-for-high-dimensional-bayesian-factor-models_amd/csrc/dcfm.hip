@@ -364,6 +364,7 @@ void dcfm_destroy(dcfm_handle *h) {
     if (h->trace) (void)hipFree(h->trace);
     if (h->probe_mem) (void)hipFree(h->probe_mem);
     if (h->prec_mem) (void)hipFree(h->prec_mem);
+    if (h->ll_mem) (void)hipFree(h->ll_mem);
     if (h->sasm && h->sasm != h->stream) (void)hipStreamDestroy(h->sasm);
     if (h->side && h->side != h->stream) (void)hipStreamDestroy(h->side);
     if (h->sdraw && h->sdraw != h->stream) (void)hipStreamDestroy(h->sdraw);
@@ -512,11 +513,12 @@ static int save_sample(dcfm_handle *h, int64_t it) {
     hipStream_t s = h->stream;
     const bool ksave = !lambda_saves(h);
     if (ksave) TRY(open_batch(h));
-    if (ksave || h->probe_n < h->probe_cap || h->prec_n < h->prec_cap) {
+    if (ksave || h->probe_n < h->probe_cap || h->prec_n < h->prec_cap || h->ll_n < h->ll_cap) {
         KTimer t(h, DCFM_K_SAVE, s);
         if (ksave) launch_save(h->d, b, b.Lb[h->lb], b.wsum[h->lb], h->batch, s, b.wslot[h->lb], h->B);
         if (h->probe_n < h->probe_cap) launch_probes(h->d, b, h->probes, h->probe_n++, s);   // dcfm_set_probes
         if (h->prec_n < h->prec_cap) launch_precision(h->d, b, h->prec, h->prec_n++, s);   // dcfm_set_precision_probes
+        if (h->ll_n < h->ll_cap) launch_loglik(h->d, b, h->ll, h->ll_n++, s);               // dcfm_set_loglik
     }
     HIPC(h, hipGetLastError());
     h->batch += 1;

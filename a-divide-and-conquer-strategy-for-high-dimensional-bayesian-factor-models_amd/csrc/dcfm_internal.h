@@ -194,6 +194,18 @@ struct Precision {
     int nv, slices;
     size_t slot, lds;
 };
+// Pointwise log-likelihood draws (loglik.hip): y_i' Sigma(s)^{-1} y_i of every training row and log det Sigma(s)
+// per saved sample.  pr: k_precision's scratch at nv = 0 (no V, no draws); T [G][NP][KW] the pass T_m = Y_m
+// Omega_m^{-1} Lambda_m and sq [G][NP] its row sums s_m (k_loglik_shard turns them in place into F_m = T_m B_m^{-1}
+// and the shards' terms s_m - (1 - rho) t.f); binv [G][K][K] the shards' B_m^{-1}; hsum [K K + 1] the
+// rank's [H_r | ld_r]; sinv [K K + 1] = [S^{-1} | log det Sigma] (one rank); draws [capacity][slot]: slot = n + 1
+// (one rank: [q | ld]) or n K + n + K K + 1 (several ranks: [U_r (n x K) | q_r | H_r | ld_r]); lds: k_loglik_close's
+// dynamic LDS bytes
+struct LogLik {
+    Precision pr;
+    double *T, *sq, *binv, *hsum, *sinv, *draws;
+    size_t slot, lds;
+};
 // Precision mean (precision_mean.hip, DCFM_FLAG_PRECISION_MEAN; all null when off).  Kept out of Bufs, which
 // the sweep's kernels take by value: Prec the accumulator (laid out as Bufs::Sigma), pfac the factor panels of
 // a flush, pscr the K x K scratch, KH the columns of a quarter of pfac (B K rounded up to ASM_KC)
@@ -336,6 +348,17 @@ void launch_trace(const Dims &d, const Bufs &b, const double *tau_cur, double *s
 void launch_probes(const Dims &d, const Bufs &b, const Probes &pr, int64_t s, hipStream_t st);
 // precision.hip: draw s of V' Sigma^{-1} V and log det Sigma from the current Lambda, omega (same place)
 void launch_precision(const Dims &d, const Bufs &b, const Precision &pr, int64_t s, hipStream_t st);
+// the same kernel at nv = 0 for loglik.hip: out [K K + 1] = the rank's sum [H_r | ld_r], binv [G][K][K] the
+// shards' B_m^{-1}.  Its scratch: precision_scratch_doubles doubles, the first precision_ticket_doubles zeroed
+// by the caller, laid out by precision_scratch_carve (which fills pr but V and draws); precision_setup once
+// before the first launch (the kernel's dynamic-LDS limit)
+void launch_precision_terms(const Dims &d, const Bufs &b, const Precision &pr, double *binv, double *out, hipStream_t st);
+size_t precision_ticket_doubles(const Dims &d);
+size_t precision_scratch_doubles(const Dims &d, int nv);
+void precision_scratch_carve(const Dims &d, int nv, double *mem, Precision &pr);
+hipError_t precision_setup();
+// loglik.hip: draw s of the rows' y_i' Sigma^{-1} y_i and log det Sigma from the current Lambda, omega (same place)
+void launch_loglik(const Dims &d, const Bufs &b, const LogLik &ll, int64_t s, hipStream_t st);
 // init.hip: dc:68-87 initial state from Philox (iteration-0 counters), delta/tau buffer 0
 void launch_init_state(const Dims &d, const Bufs &b, hipStream_t s);
 // kernels.hip: one iteration's variates into the draw buffers (side-stream layouts)

@@ -80,6 +80,10 @@ struct dcfm_handle {
     double *prec_mem = nullptr;
     Precision prec{};
     int64_t prec_cap = 0, prec_n = 0;
+    // pointwise log-likelihood draws (dcfm_set_loglik, loglik.hip): the same, independent of both
+    double *ll_mem = nullptr;
+    LogLik ll{};
+    int64_t ll_cap = 0, ll_n = 0;
     // posterior mean of the precision matrix (DCFM_FLAG_PRECISION_MEAN, precision_mean.hip): null when off
     PrecMean pm{};
     bool prof = false;

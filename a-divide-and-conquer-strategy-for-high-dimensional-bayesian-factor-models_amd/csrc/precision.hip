@@ -128,7 +128,8 @@ __global__ __launch_bounds__(256) void k_precision(const double *__restrict__ La
                                                    const double *__restrict__ V, int P, int PP, int KW, int K, int G,
                                                    int nv, double rho, int form, double *part, double *gram,
                                                    double *term, double *gterm, double *rsum, double *xs,
-                                                   unsigned *ticket, double *__restrict__ draw) {
+                                                   unsigned *ticket, double *__restrict__ draw,
+                                                   double *__restrict__ binv) {
     extern __shared__ __align__(16) double dyn[];
     __shared__ double red[256];
     __shared__ unsigned flag;
@@ -220,6 +221,8 @@ __global__ __launch_bounds__(256) void k_precision(const double *__restrict__ La
     double *A = dyn, *sP = dyn + K * K, *Cc = sP + (K & 1);   // Cc: 16-byte aligned inside the idle panel
     load_shifted(A, K, Mg, w, 1.0 - rho);                 // B_m = I + (1 - rho) G_m
     const double ldB = gj_invert(A, K, Cc);
+    if (binv)                                             // loglik.hip keeps B_m^{-1} (read by a later launch)
+        for (int e = t; e < K * K; e += 256) binv[(size_t)m * K * K + e] = A[e];
     mat_apply(A, K, Mg, w, w, tm, w, sP);                 // [H_m | F_m] = B^{-1} [G_m | U_m]
     stores_done();
     close_quad<true>(Mg + K, w, tm + K, w, K, nv, 1.0 - rho, Mg + (size_t)K * w + K, w, tm + (size_t)K * w, dyn,
@@ -249,13 +252,47 @@ __global__ __launch_bounds__(256) void k_precision(const double *__restrict__ La
 void launch_precision(const Dims &d, const Bufs &b, const Precision &pr, int64_t s, hipStream_t st) {
     hipLaunchKernelGGL(k_precision, dim3(pr.slices, d.G), dim3(256), pr.lds, st, b.Lam, b.omega, pr.V, d.P, d.PP, d.kp,
                        d.K, d.G, pr.nv, d.rho, d.coll ? 0 : 1, pr.part, pr.gram, pr.term, pr.gterm, pr.rsum, pr.xs,
-                       pr.ticket, pr.draws + (size_t)s * pr.slot);
+                       pr.ticket, pr.draws + (size_t)s * pr.slot, nullptr);
 }
 
-}  // namespace dcfm
+// loglik.hip: the stages at nv = 0 -- out = the rank's sum [H_r (K x K) | ld_r], binv [G][K][K] the shards' B_m^{-1}
+void launch_precision_terms(const Dims &d, const Bufs &b, const Precision &pr, double *binv, double *out, hipStream_t st) {
+    hipLaunchKernelGGL(k_precision, dim3(pr.slices, d.G), dim3(256), pr.lds, st, b.Lam, b.omega, nullptr, d.P, d.PP, d.kp,
+                       d.K, d.G, 0, d.rho, 0, pr.part, pr.gram, pr.term, pr.gterm, pr.rsum, pr.xs, pr.ticket, out, binv);
+}
 
 static int prec_groups(int G) { return (G + PROBE_FAN - 1) / PROBE_FAN; }
 static size_t prec_ticket_doubles(int G) { return ((size_t)G + prec_groups(G) + 1 + 1) / 2; }
+
+// k_precision's scratch for nv probes: [ticket | part | gram | term, gterm, rsum | xs] (dcfm_internal.h has the
+// sizes); the caller zeroes the first precision_ticket_doubles (the tickets start at 0)
+size_t precision_ticket_doubles(const Dims &d) { return prec_ticket_doubles(d.G); }
+size_t precision_scratch_doubles(const Dims &d, int nv) {
+    const size_t w = (size_t)d.K + nv, ts = (size_t)d.K * w + (size_t)nv * nv + 1, ps = (size_t)precision_tiles(d.K, nv) * 256 + 1;
+    return prec_ticket_doubles(d.G) + (size_t)d.G * precision_slices(d.G, d.P, d.K, nv) * ps + (size_t)d.G * w * w +
+           ((size_t)d.G + prec_groups(d.G) + 1) * ts + (size_t)d.K * nv;
+}
+void precision_scratch_carve(const Dims &d, int nv, double *mem, Precision &pr) {
+    const size_t w = (size_t)d.K + nv, ts = (size_t)d.K * w + (size_t)nv * nv + 1, ps = (size_t)precision_tiles(d.K, nv) * 256 + 1;
+    pr.nv = nv;
+    pr.slices = precision_slices(d.G, d.P, d.K, nv);
+    pr.lds = precision_lds_doubles(d.K, nv) * sizeof(double);
+    pr.ticket = reinterpret_cast<unsigned *>(mem);
+    pr.part = mem + prec_ticket_doubles(d.G);
+    pr.gram = pr.part + (size_t)d.G * pr.slices * ps;
+    pr.term = pr.gram + (size_t)d.G * w * w;
+    pr.gterm = pr.term + (size_t)d.G * ts;
+    pr.rsum = pr.gterm + (size_t)prec_groups(d.G) * ts;
+    pr.xs = pr.rsum + ts;
+}
+// the largest footprint (K = 128, nv = 32: 146 KB) passes the default limit of dynamic LDS; the attribute
+// belongs to the kernel, not the handle, so it is set to that whatever this handle's K
+hipError_t precision_setup() {
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(k_precision), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)(precision_lds_doubles(KP_MAX, PROBE_NV_MAX) * sizeof(double)));
+}
+
+}  // namespace dcfm
 
 // Host close of the several-rank read-out: t = [H | F (K x w) | q (nv x nv) | ld] summed over the ranks;
 // S = I + rho H = R R' (plain Cholesky of the lower triangle), T = R^{-1} F, Q = q - rho T'T (one triangle,
@@ -310,33 +347,19 @@ int dcfm_set_precision_probes(dcfm_handle *h, const double *V, int32_t nv, int64
     h->prec_cap = h->prec_n = 0;
     if (capacity == 0) return DCFM_OK;
     Precision pr{};
-    pr.nv = nv;
-    pr.slices = precision_slices(d.G, d.P, d.K, nv);
-    pr.lds = precision_lds_doubles(d.K, nv) * sizeof(double);
-    // the largest footprint (K = 128, nv = 32: 146 KB) passes the default limit of dynamic LDS; the attribute
-    // belongs to the kernel, not the handle, so it is set to that whatever this handle's K
-    HIPC(h, hipFuncSetAttribute(reinterpret_cast<const void *>(k_precision), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)(precision_lds_doubles(KP_MAX, PROBE_NV_MAX) * sizeof(double))));
-    const size_t rows = (size_t)d.G * d.P, w = (size_t)d.K + nv, ts = (size_t)d.K * w + (size_t)nv * nv + 1,
-                 ps = (size_t)precision_tiles(d.K, nv) * 256 + 1;
+    HIPC(h, precision_setup());
+    const size_t rows = (size_t)d.G * d.P, w = (size_t)d.K + nv, ts = (size_t)d.K * w + (size_t)nv * nv + 1;
     pr.slot = d.coll ? ts : (size_t)nv * nv + 1;
-    const size_t ntk = prec_ticket_doubles(d.G), nV = rows * nv, npart = (size_t)d.G * pr.slices * ps,
-                 ngram = (size_t)d.G * w * w, nterm = ((size_t)d.G + prec_groups(d.G) + 1) * ts, nxs = (size_t)d.K * nv;
+    const size_t nscr = precision_scratch_doubles(d, nv), nV = rows * nv;
     void *q = nullptr;
-    if (hipMalloc(&q, (ntk + nV + npart + ngram + nterm + nxs + (size_t)capacity * pr.slot) * sizeof(double)) != hipSuccess)
+    if (hipMalloc(&q, (nscr + nV + (size_t)capacity * pr.slot) * sizeof(double)) != hipSuccess)
         return fail(h, DCFM_ERR_ALLOC, "set_precision_probes: %lld draws of %d probes", (long long)capacity, (int)nv);
     h->prec_mem = static_cast<double *>(q);
-    pr.ticket = reinterpret_cast<unsigned *>(h->prec_mem);
-    double *dV = h->prec_mem + ntk;
+    precision_scratch_carve(d, nv, h->prec_mem, pr);
+    double *dV = h->prec_mem + nscr;
     pr.V = dV;
-    pr.part = dV + nV;
-    pr.gram = pr.part + npart;
-    pr.term = pr.gram + ngram;
-    pr.gterm = pr.term + (size_t)d.G * ts;
-    pr.rsum = pr.gterm + (size_t)prec_groups(d.G) * ts;
-    pr.xs = pr.term + nterm;
-    pr.draws = pr.xs + nxs;
-    HIPC(h, hipMemset(h->prec_mem, 0, ntk * sizeof(double)));   // tickets start at 0
+    pr.draws = dV + nV;
+    HIPC(h, hipMemset(h->prec_mem, 0, precision_ticket_doubles(d) * sizeof(double)));   // tickets start at 0
     if (nV) {   // this rank's rows of V, row-major
         std::vector<double> loc(nV);
         const size_t row0 = (size_t)d.shard0 * d.P;

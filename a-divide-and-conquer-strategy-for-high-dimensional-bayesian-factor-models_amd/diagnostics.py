@@ -128,6 +128,34 @@ def heldout_log_density(Q, logdet, p) -> dict:
     return {"per_sample": per, "lppd": lppd, "total": float(lppd.sum())}
 
 
+def waic(ll) -> dict:
+    """WAIC (Watanabe 2010; Gelman, Hwang and Vehtari 2014) from the pointwise log-likelihood draws ``ll`` of
+    shape (S, n), S >= 2 saved samples by n training rows (``Sampler.loglik_draws``).  Per point: ``lppd_i``,
+    the log of the mean over s of the densities (log-mean-exp, shifted by the maximum as in
+    ``heldout_log_density``), ``p_waic_i``, the sample variance of ll over s (ddof = 1), and
+    ``elpd_i = lppd_i - p_waic_i``.  Totals: ``lppd``, ``p_waic`` (the effective number of parameters),
+    ``elpd_waic``, ``waic = -2 elpd_waic`` and ``se = sqrt(n var_i(elpd_i))`` (ddof = 1), the standard error of elpd_waic.
+    The units are standardised (the data the sweep holds): a density in the original units subtracts
+    ``sum(log sd)`` over the kept columns from every ll[s, i].  Chains that are compared (over g, k, rho) must
+    use the same Y.  A ``p_waic_i`` above 0.4 is the usual warning sign that WAIC is unreliable for that point
+    (Vehtari, Gelman and Gabry 2017); PSIS-LOO takes the same ``ll``."""
+    ll = np.asarray(ll, dtype=np.float64)
+    if ll.ndim != 2 or ll.shape[0] < 2:
+        raise ValueError(f"ll must be (S, n) with S >= 2, got {ll.shape}")
+    n = ll.shape[1]
+    top = ll.max(axis=0)
+    safe = np.where(np.isfinite(top), top, 0.0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        lppd_i = safe + np.log(np.mean(np.exp(ll - safe), axis=0))
+        p_i = ll.var(axis=0, ddof=1)
+    elpd_i = lppd_i - p_i
+    elpd = float(elpd_i.sum())
+    with np.errstate(invalid="ignore"):
+        se = float(np.sqrt(n * elpd_i.var(ddof=1))) if n > 1 else 0.0   # var over the points with ddof = 1
+    return {"lppd_i": lppd_i, "p_waic_i": p_i, "elpd_i": elpd_i, "lppd": float(lppd_i.sum()),
+            "p_waic": float(p_i.sum()), "elpd_waic": elpd, "waic": -2.0 * elpd, "se": se}
+
+
 def partial_correlations(T) -> np.ndarray:
     """Partial correlations from a precision matrix T (``Sampler.get_precision_mean``, or any symmetric
     p x p precision): ``-T_ab / sqrt(T_aa T_bb)`` off the diagonal, the correlation of variables a and b

@@ -23,6 +23,7 @@ import time
 
 import numpy as np
 
+from .diagnostics import waic as _waic
 from .sampler import Hyper, Sampler, count_nonzero_columns
 
 
@@ -135,7 +136,7 @@ def local_state(state: dict, s0: int, gl: int) -> dict:
 def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hyper(),
                   init_draws=None, iter_draws=None, nranks=1, rank=0, device=0, comm_uid=None,
                   asm_batch=0, return_info=False, device_ingest=True, device_init=True, return_sd=False,
-                  n_components=0, rhs=None, probes=None, precision_probes=None, return_precision=False):
+                  n_components=0, rhs=None, probes=None, precision_probes=None, return_precision=False, loglik=False):
     """Sigmaout = divideconquer(Y,g,k,BURNIN,MCMC,thin,rho)   (divideconquer.m:1).
 
     ``device_ingest`` (default): the zero-column scan and the partition/standardisation
@@ -198,6 +199,13 @@ def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hy
     ``diagnostics.heldout_log_density(draws, logdet, p)`` gives the per-sample densities and their
     log-mean-exp (lppd) in the standardised units; a density in the original units subtracts
     ``sum(log sd)`` over the kept columns.
+
+    ``loglik``: the pointwise log-likelihood of the training rows needs no held-out data: with True,
+    ``ll[s, i] = log N(y_i; 0, Sigma(s))`` of every row i of the standardised data under every saved sample s
+    is recorded on the device (Sampler.set_loglik, capacity mcmc // thin) and a dict ``{"ll", "logdet",
+    "waic"}`` -- ll (S, n), logdet (S,) and ``diagnostics.waic(ll)`` (lppd, p_waic, elpd_waic, waic, se and the
+    per-point terms) -- is appended after the ``precision_probes`` dict (if requested) and before info.
+    Standardised units, as above; runs that are compared over g, k or rho must use the same Y.
     """
     t0 = time.perf_counter()                                     # dc:29 tic
     if device_ingest:
@@ -240,6 +248,8 @@ def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hy
             smp.set_probes(permute_vectors(probes, keep, init.varind))
         if precision_probes is not None:
             smp.set_precision_probes(permute_vectors(precision_probes, keep, init.varind))
+        if loglik:
+            smp.set_loglik()
         smp.run(1, N)                                            # dc:90-197
         Sigmaout = smp.get_sigma()
         Sigmasd = smp.get_sigma_moment("sd") if return_sd else None
@@ -257,6 +267,10 @@ def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hy
         if precision_probes is not None:
             q, ld = smp.precision_draws()
             prc = {"draws": q, "logdet": ld, "mean": q.mean(axis=0), "sd": q.std(axis=0)}
+        llk = None
+        if loglik:
+            ll, _, ld = smp.loglik_draws(parts=True)
+            llk = {"ll": ll, "logdet": ld, "waic": _waic(ll) if ll.shape[0] >= 2 else None}   # waic needs two samples
     finally:
         smp.close()
     elapsed = time.perf_counter() - t0                           # dc:200 toc
@@ -271,6 +285,8 @@ def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hy
         out += (prb,)
     if precision_probes is not None:
         out += (prc,)
+    if loglik:
+        out += (llk,)
     if return_info:
         out += ({"varind": np.asarray(init.varind), "keep": keep, "n": n, "p": p, "P": P,
                  "K": K, "N": N, "seconds": elapsed},)

@@ -453,6 +453,33 @@ class Sampler:
         self._check(self.lib.dcfm_get_precision_draws(self.h, _ptr(Q), _ptr(ld), C.byref(cnt)))
         return Q[:cnt.value].copy(), ld[:cnt.value].copy()
 
+    # -- pointwise log-likelihood draws ------------------------------------------------
+    def set_loglik(self, capacity=None):
+        """Record, for every saved sample s of later runs, ``y_i' Sigma(s)^-1 y_i`` of every row i of the
+        standardised data the sweep holds and ``log det Sigma(s)`` (dcfm_set_loglik).  Up to ``capacity``
+        draws are held (default ``mcmc // thin``); later saved samples are not recorded.  Calling it again
+        resets the count; ``set_loglik(0)`` turns the recording off and frees its buffers.  Independent of
+        ``set_probes`` and ``set_precision_probes``: all three may be on at once."""
+        if capacity is None:
+            capacity = int(self.cfg.mcmc) // int(self.cfg.thin)
+        self._check(self.lib.dcfm_set_loglik(self.h, int(capacity)))
+        self._ll_cap = int(capacity)
+
+    def loglik_draws(self, parts=False):
+        """``ll`` of shape (S, n): ``ll[s, i] = log N(y_i; 0, Sigma(s)) = -(p log 2 pi + logdet[s] + maha[s, i]) / 2``,
+        the pointwise log-likelihood of training row i (Y's row order, standardised units) under saved sample
+        s -- the input of ``diagnostics.waic``.  ``parts=True`` returns ``(ll, maha, logdet)`` with maha (S, n)
+        and logdet (S,).  Shapes (0, n) and (0,) when nothing is recorded.  Collective when nranks > 1: every
+        rank calls it and receives the same bytes."""
+        cap = getattr(self, "_ll_cap", 0)
+        cnt = C.c_int64(0)
+        maha = np.zeros((max(cap, 1), self.n), dtype=np.float64)          # one (collective) call
+        ld = np.zeros(max(cap, 1), dtype=np.float64)
+        self._check(self.lib.dcfm_get_loglik(self.h, _ptr(maha), _ptr(ld), C.byref(cnt)))
+        maha, ld = maha[:cnt.value].copy(), ld[:cnt.value].copy()
+        ll = -0.5 * (self.P * self.g * np.log(2.0 * np.pi) + ld[:, None] + maha)
+        return (ll, maha, ld) if parts else ll
+
     # -- measurement -----------------------------------------------------------------
     def set_profiling(self, on: bool):
         self._check(self.lib.dcfm_set_profiling(self.h, 1 if on else 0))

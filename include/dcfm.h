@@ -408,6 +408,42 @@ int  dcfm_get_probe_draws(dcfm_handle *h, double *out, int64_t *count);
 int  dcfm_set_precision_probes(dcfm_handle *h, const double *V, int32_t nv, int64_t capacity);
 int  dcfm_get_precision_draws(dcfm_handle *h, double *Q, double *logdet, int64_t *count);
 
+/* ---- pointwise log-likelihood of the training rows per saved sample (WAIC, PSIS-LOO) ----
+ * l[s, i] = log N(y_i; 0, Sigma(s)) = -(p log 2 pi + log det Sigma(s) + y_i' Sigma(s)^{-1} y_i) / 2 for every
+ * saved sample s and every row i = 1..n of the standardised data the sweep holds (dcfm_get_data), which is what
+ * model comparison over g, K and rho needs and no held-out data.  The device records the Mahalanobis part
+ * q_i = y_i' Sigma(s)^{-1} y_i and log det Sigma(s) by the recursion of the precision draws with the data rows
+ * in the probes' place: one more fp64-MFMA pass over Y per saved sample (T_m = Y_m Omega_m^{-1} Lambda_m, the
+ * bytes and MFMAs of the sweep's W pass), the shards' K x K inversions, and n K^2 g flops to close the rows
+ * (csrc/loglik.hip has the recursion and the launch chain).
+ *
+ * dcfm_set_loglik: from the next dcfm_run on every saved sample records one draw until `capacity` draws are
+ * held; later saved samples are not recorded; a second call resets the count; capacity == 0 turns it off and
+ * frees its buffers; nothing is allocated or launched until a call with capacity > 0.  Not collective.  It needs
+ * no data at call time (the data must be set before the run that records).  Booked under DCFM_K_SAVE.  No
+ * floating-point atomics and fixed summation orders: the same inputs give the same bits, in one dcfm_run call or
+ * one iteration per call.  Independent of dcfm_set_probes and dcfm_set_precision_probes: all three may be on at
+ * once and none changes another's bits.
+ * Device bytes: 8 (g_local NP (KW + 1) + g_local K^2 + 2 (K^2 + 1) + capacity * slot + scratch), NP = n rounded
+ * up to 128 and KW = K padded to 32 / 64 / 128: the pass's T_m and row sums, the shards' B_m^{-1}, the rank's
+ * [H | ld] and [S^{-1} | ld]; slot = n + 1 on one rank ([q | ld]) and n K + n + K^2 + 1 on several (the rank's
+ * [U_r | q_r | H_r | ld_r]); scratch = that of dcfm_set_precision_probes at nv = 0.  LDS: the Y pass none, the
+ * K x K stages up to 8 (K^2 + 16 K) bytes + 2 KiB (the precision draws' kernel), the close 8 ((K + 16) (K | 1) +
+ * 272) bytes (147 KiB at K = 128).
+ * Errors (DCFM_ERR_INVALID, the setting made before stays as it was): NULL handle ("null handle"), capacity < 0.
+ *
+ * dcfm_get_loglik: count (required) receives the number of draws held; maha (nullable) the n x count
+ * column-major array, q_i of draw s at maha[s * n + i], in saved-sample order and Y's row order (the padding
+ * rows of the device layouts never reach it); logdet (nullable) the count values of log det Sigma(s).  Blocks
+ * (synchronises the sweep stream) and does not disturb a later dcfm_run.  With nothing set *count = 0 and
+ * DCFM_OK.  After a run that ended in DCFM_ERR_NUMERIC it returns what the device holds: a NaN state gives NaN
+ * draws (no stage takes a data-dependent trip count).  With nranks > 1 it is collective: every rank's partial
+ * of all draws travels in one all-gather, every rank adds them in rank order and closes the K x K step and
+ * rho u' S^{-1} u on the host (a plain Cholesky), and every rank receives identical bytes; one rank closes it
+ * in the kernel.  Errors (DCFM_ERR_INVALID): NULL handle ("null handle"), NULL count ("null argument"). */
+int  dcfm_set_loglik(dcfm_handle *h, int64_t capacity);
+int  dcfm_get_loglik(dcfm_handle *h, double *maha, double *logdet, int64_t *count);
+
 /* ---- measurement --------------------------------------------------------- */
 /* Per-kernel HIP-event timing on the handle's stream (off by default).
  * Kernel ids: DCFM_K_* below.  Times are accumulated device milliseconds. */

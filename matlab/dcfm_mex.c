@@ -46,6 +46,11 @@
  *                                         coordinates; capacity as for 'set_probes'; independent of it
  *   [Q, logdet] = dcfm_mex('precision_draws', h)   the recorded draws, nv x nv x S and S x 1 (empty with
  *                                         nothing set)
+ *   dcfm_mex('set_loglik', h[, capacity])  record maha(i,s) = y_i' * inv(Sigma_s) * y_i of every row y_i of the
+ *                                         standardised data and logdet(s) for every saved sample s of later
+ *                                         runs; capacity as for 'set_probes'; independent of both
+ *   [maha, logdet] = dcfm_mex('loglik', h)   the recorded draws, n x S and S x 1 (n x 0 and 0 x 1 with nothing
+ *                                         set); log N(y_i; 0, Sigma_s) = -(p*log(2*pi) + logdet(s) + maha(i,s))/2
  *   e = dcfm_mex('error', h, U, s, iters)[||S-S0||_F, ||S0||_F, ||S-S0||_2] vs S0 = UU' + diag(s)
  *   dcfm_mex('set_trace', h, cap); T = dcfm_mex('get_trace', h)     chain trace (count x 4)
  *   dcfm_mex('destroy', h)
@@ -444,6 +449,26 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         mxArray *ld = mxCreateDoubleMatrix((mwSize)cnt, 1, mxREAL);
         if (cnt > 0) ck(t->h, dcfm_get_precision_draws(t->h, nv > 0 ? mxGetDoubles(Q) : NULL, mxGetDoubles(ld), &cnt));
         plhs[0] = Q;
+        if (nlhs > 1) plhs[1] = ld;
+        else mxDestroyArray(ld);
+    } else if (!strcmp(cmd, "set_loglik")) {         /* dcfm_mex('set_loglik', h[, capacity]) */
+        if (nrhs != 2 && nrhs != 3)
+            mexErrMsgIdAndTxt("dcfm:nargs", "'%s' takes 1 or 2 arguments, got %d", cmd, nrhs - 1);
+        /* the argument that needs no handle first: a malformed call never reaches the library */
+        const double cap = nrhs > 2 ? scalar(prhs[2], "capacity") : -1;
+        if (nrhs > 2 && (cap < 0 || cap > 9007199254740992.0 || cap != (double)(int64_t)cap))
+            mexErrMsgIdAndTxt("dcfm:arg", "capacity must be a non-negative integer");
+        slot *t = get(prhs[1]);
+        ck(t->h, dcfm_set_loglik(t->h, nrhs > 2 ? (int64_t)cap : (t->thin > 0 ? t->mcmc / t->thin : 0)));
+    } else if (!strcmp(cmd, "loglik")) {             /* [maha, logdet] = dcfm_mex('loglik', h) */
+        nargs(nrhs, 2, cmd);
+        slot *t = get(prhs[1]);
+        int64_t cnt = 0;
+        ck(t->h, dcfm_get_loglik(t->h, NULL, NULL, &cnt));
+        mxArray *q = mxCreateDoubleMatrix((mwSize)t->n, (mwSize)cnt, mxREAL);   /* the sizes the library writes */
+        mxArray *ld = mxCreateDoubleMatrix((mwSize)cnt, 1, mxREAL);
+        if (cnt > 0) ck(t->h, dcfm_get_loglik(t->h, mxGetDoubles(q), mxGetDoubles(ld), &cnt));
+        plhs[0] = q;
         if (nlhs > 1) plhs[1] = ld;
         else mxDestroyArray(ld);
     } else if (!strcmp(cmd, "destroy")) {

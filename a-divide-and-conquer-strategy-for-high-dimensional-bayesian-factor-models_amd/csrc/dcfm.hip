@@ -365,6 +365,7 @@ void dcfm_destroy(dcfm_handle *h) {
     if (h->probe_mem) (void)hipFree(h->probe_mem);
     if (h->prec_mem) (void)hipFree(h->prec_mem);
     if (h->ll_mem) (void)hipFree(h->ll_mem);
+    if (h->pred_mem) (void)hipFree(h->pred_mem);
     if (h->sasm && h->sasm != h->stream) (void)hipStreamDestroy(h->sasm);
     if (h->side && h->side != h->stream) (void)hipStreamDestroy(h->side);
     if (h->sdraw && h->sdraw != h->stream) (void)hipStreamDestroy(h->sdraw);
@@ -513,12 +514,14 @@ static int save_sample(dcfm_handle *h, int64_t it) {
     hipStream_t s = h->stream;
     const bool ksave = !lambda_saves(h);
     if (ksave) TRY(open_batch(h));
-    if (ksave || h->probe_n < h->probe_cap || h->prec_n < h->prec_cap || h->ll_n < h->ll_cap) {
+    if (ksave || h->probe_n < h->probe_cap || h->prec_n < h->prec_cap || h->ll_n < h->ll_cap ||
+        h->pred_n < h->pred_cap) {
         KTimer t(h, DCFM_K_SAVE, s);
         if (ksave) launch_save(h->d, b, b.Lb[h->lb], b.wsum[h->lb], h->batch, s, b.wslot[h->lb], h->B);
         if (h->probe_n < h->probe_cap) launch_probes(h->d, b, h->probes, h->probe_n++, s);   // dcfm_set_probes
         if (h->prec_n < h->prec_cap) launch_precision(h->d, b, h->prec, h->prec_n++, s);   // dcfm_set_precision_probes
         if (h->ll_n < h->ll_cap) launch_loglik(h->d, b, h->ll, h->ll_n++, s);               // dcfm_set_loglik
+        if (h->pred_n < h->pred_cap) launch_predict(h->d, b, h->pred, h->pred_n++, s);      // dcfm_set_predict
     }
     HIPC(h, hipGetLastError());
     h->batch += 1;

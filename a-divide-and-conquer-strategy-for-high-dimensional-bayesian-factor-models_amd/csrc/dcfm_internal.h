@@ -206,6 +206,17 @@ struct LogLik {
     double *T, *sq, *binv, *hsum, *sinv, *draws;
     size_t slot, lds;
 };
+// Conditional prediction (predict.hip): pr k_precision's scratch at nv = T with pr.V = the new rows Y* [G P][T]
+// (row-major, the unobserved entries zero; no pr.draws); obs [G P] the 0 / 1 mask; sinv [K][K] = S^{-1} and qd
+// [T T + 1] = [q | ld] of the sample in flight; work [G][4 K K + 2 K T] the K x K products of k_predict_prod; coef
+// [G][K4][wc] = [t_m (Tp columns) | N_m (16 ceil(K / 16))] zero-padded, K4 = K rounded up to 4, Tp = T to 16;
+// the accumulators sum, sum2 [G P][T] and cvsum [G P]; draws [capacity][T + 1] = [diag q | ld]
+struct Predict {
+    Precision pr;
+    unsigned char *obs;
+    double *sinv, *qd, *work, *coef, *sum, *sum2, *cvsum, *draws;
+    int T, Tp, wc;
+};
 // Precision mean (precision_mean.hip, DCFM_FLAG_PRECISION_MEAN; all null when off).  Kept out of Bufs, which
 // the sweep's kernels take by value: Prec the accumulator (laid out as Bufs::Sigma), pfac the factor panels of
 // a flush, pscr the K x K scratch, KH the columns of a quarter of pfac (B K rounded up to ASM_KC)
@@ -357,6 +368,13 @@ size_t precision_ticket_doubles(const Dims &d);
 size_t precision_scratch_doubles(const Dims &d, int nv);
 void precision_scratch_carve(const Dims &d, int nv, double *mem, Precision &pr);
 hipError_t precision_setup();
+// the one-rank form with the Gram's weight masked by obs [G][P] (an unobserved row: weight 0, log term 0) and pr.V
+// the new rows: draw = [q (nv x nv) | ld] of Sigma_AA, sinv [K][K] = S^{-1}; pr.term, pr.rsum, pr.xs are left holding
+// [H_m | F_m], [H | F] and S^{-1} F
+void launch_precision_masked(const Dims &d, const Bufs &b, const Precision &pr, const unsigned char *obs, double *sinv,
+                             double *draw, hipStream_t st);
+// predict.hip: sample s of the conditional prediction from the current Lambda, omega (same place, one rank)
+void launch_predict(const Dims &d, const Bufs &b, const Predict &pd, int64_t s, hipStream_t st);
 // loglik.hip: draw s of the rows' y_i' Sigma^{-1} y_i and log det Sigma from the current Lambda, omega (same place)
 void launch_loglik(const Dims &d, const Bufs &b, const LogLik &ll, int64_t s, hipStream_t st);
 // init.hip: dc:68-87 initial state from Philox (iteration-0 counters), delta/tau buffer 0

@@ -84,6 +84,10 @@ struct dcfm_handle {
     double *ll_mem = nullptr;
     LogLik ll{};
     int64_t ll_cap = 0, ll_n = 0;
+    // conditional prediction (dcfm_set_predict, predict.hip): the same, independent of the three
+    double *pred_mem = nullptr;
+    Predict pred{};
+    int64_t pred_cap = 0, pred_n = 0;
     // posterior mean of the precision matrix (DCFM_FLAG_PRECISION_MEAN, precision_mean.hip): null when off
     PrecMean pm{};
     bool prof = false;

@@ -129,7 +129,8 @@ __global__ __launch_bounds__(256) void k_precision(const double *__restrict__ La
                                                    int nv, double rho, int form, double *part, double *gram,
                                                    double *term, double *gterm, double *rsum, double *xs,
                                                    unsigned *ticket, double *__restrict__ draw,
-                                                   double *__restrict__ binv) {
+                                                   double *__restrict__ binv,
+                                                   const unsigned char *__restrict__ obs, double *__restrict__ sinv) {
     extern __shared__ __align__(16) double dyn[];
     __shared__ double red[256];
     __shared__ unsigned flag;
@@ -164,9 +165,12 @@ __global__ __launch_bounds__(256) void k_precision(const double *__restrict__ La
             sX[e] = v;
         }
         if (t < nr4) {
+            // predict.hip's mask: an unobserved row takes weight 0 and log term 0 by selects (its omega need not be
+            // invertible); obs null: every row of the slice counts
+            const bool on = t < nr && (!obs || obs[(size_t)m * P + r0 + t] != 0);
             const double o = t < nr ? om[r0 + t] : 1.0;
-            sW[t] = t < nr ? 1.0 / o : 0.0;
-            lw += log(o);
+            sW[t] = on ? 1.0 / o : 0.0;
+            lw += on ? log(o) : 0.0;
         }
         __syncthreads();
         for (int r = 0; r < nr4; r += 4) {
@@ -243,6 +247,8 @@ __global__ __launch_bounds__(256) void k_precision(const double *__restrict__ La
     stores_done();
     load_shifted(A, K, rsum, w, rho);                     // S = I + rho H
     const double ldS = gj_invert(A, K, Cc);
+    if (sinv)                                             // predict.hip keeps S^{-1} (read by a later launch)
+        for (int e = t; e < K * K; e += 256) sinv[e] = A[e];
     mat_apply(A, K, rsum + K, w, nv, xs, nv, sP);         // S^{-1} F
     stores_done();
     close_quad<false>(rsum + K, w, xs, nv, K, nv, rho, rsum + (size_t)K * w, nv, draw, dyn, dyn + K * PROBE_NV_MAX);
@@ -252,13 +258,23 @@ __global__ __launch_bounds__(256) void k_precision(const double *__restrict__ La
 void launch_precision(const Dims &d, const Bufs &b, const Precision &pr, int64_t s, hipStream_t st) {
     hipLaunchKernelGGL(k_precision, dim3(pr.slices, d.G), dim3(256), pr.lds, st, b.Lam, b.omega, pr.V, d.P, d.PP, d.kp,
                        d.K, d.G, pr.nv, d.rho, d.coll ? 0 : 1, pr.part, pr.gram, pr.term, pr.gterm, pr.rsum, pr.xs,
-                       pr.ticket, pr.draws + (size_t)s * pr.slot, nullptr);
+                       pr.ticket, pr.draws + (size_t)s * pr.slot, nullptr, nullptr, nullptr);
+}
+
+// predict.hip: the one-rank form with pr.V = the new rows, the weight masked by obs [G][P]: draw = [q (nv x nv) | ld]
+// of Sigma_AA(s), sinv = S^{-1}; pr.term, pr.rsum and pr.xs keep [H_m | F_m], [H | F] and S^{-1} F for the next launch
+void launch_precision_masked(const Dims &d, const Bufs &b, const Precision &pr, const unsigned char *obs, double *sinv,
+                             double *draw, hipStream_t st) {
+    hipLaunchKernelGGL(k_precision, dim3(pr.slices, d.G), dim3(256), pr.lds, st, b.Lam, b.omega, pr.V, d.P, d.PP, d.kp,
+                       d.K, d.G, pr.nv, d.rho, 1, pr.part, pr.gram, pr.term, pr.gterm, pr.rsum, pr.xs, pr.ticket, draw,
+                       nullptr, obs, sinv);
 }
 
 // loglik.hip: the stages at nv = 0 -- out = the rank's sum [H_r (K x K) | ld_r], binv [G][K][K] the shards' B_m^{-1}
 void launch_precision_terms(const Dims &d, const Bufs &b, const Precision &pr, double *binv, double *out, hipStream_t st) {
     hipLaunchKernelGGL(k_precision, dim3(pr.slices, d.G), dim3(256), pr.lds, st, b.Lam, b.omega, nullptr, d.P, d.PP, d.kp,
-                       d.K, d.G, 0, d.rho, 0, pr.part, pr.gram, pr.term, pr.gterm, pr.rsum, pr.xs, pr.ticket, out, binv);
+                       d.K, d.G, 0, d.rho, 0, pr.part, pr.gram, pr.term, pr.gterm, pr.rsum, pr.xs, pr.ticket, out, binv,
+                       nullptr, nullptr);
 }
 
 static int prec_groups(int G) { return (G + PROBE_FAN - 1) / PROBE_FAN; }

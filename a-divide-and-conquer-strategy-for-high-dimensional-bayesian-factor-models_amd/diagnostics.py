@@ -128,6 +128,31 @@ def heldout_log_density(Q, logdet, p) -> dict:
     return {"per_sample": per, "lppd": lppd, "total": float(lppd.sum())}
 
 
+def conditional_log_density(maha, logdet, n_obs) -> dict:
+    """Log density of partly observed rows from the conditional prediction's draws (``Sampler.predict``): with
+    ``maha[s, t] = y_A' Sigma_AA(s)^-1 y_A`` (S, nt) of new row t, ``logdet[s] = log det Sigma_AA(s)`` (S,) and
+    ``n_obs = |A|`` the number of observed variables, returns ``per_sample`` (S, nt),
+    ``-(n_obs log 2 pi + logdet[s] + maha[s, t]) / 2``, the log density of the observed part of row t under
+    sample s; ``lppd`` (nt,), the log of the mean over s of the densities (log-mean-exp, shifted by the maximum
+    as in ``heldout_log_density``), and ``total``, the sum of lppd.  The units are standardised (the
+    coordinates the sweep works in): a density in the data's units subtracts ``sum_{j in A} log sd_j``, sd the
+    training columns' standard deviations."""
+    q = np.asarray(maha, dtype=np.float64)
+    ld = np.asarray(logdet, dtype=np.float64).reshape(-1)
+    if q.ndim == 1:
+        q = q[:, None]
+    if q.ndim != 2 or q.shape[0] < 1 or ld.shape[0] != q.shape[0]:
+        raise ValueError(f"maha must be (S, nt) and logdet (S,) with S >= 1, got {q.shape} and {ld.shape}")
+    per = -0.5 * (float(n_obs) * np.log(2.0 * np.pi) + ld[:, None] + q)
+    if per.shape[1] == 0:
+        return {"per_sample": per, "lppd": np.zeros(0), "total": 0.0}
+    top = per.max(axis=0)
+    safe = np.where(np.isfinite(top), top, 0.0)
+    with np.errstate(divide="ignore"):
+        lppd = safe + np.log(np.mean(np.exp(per - safe), axis=0))
+    return {"per_sample": per, "lppd": lppd, "total": float(lppd.sum())}
+
+
 def waic(ll) -> dict:
     """WAIC (Watanabe 2010; Gelman, Hwang and Vehtari 2014) from the pointwise log-likelihood draws ``ll`` of
     shape (S, n), S >= 2 saved samples by n training rows (``Sampler.loglik_draws``).  Per point: ``lppd_i``,

@@ -23,7 +23,7 @@ import time
 
 import numpy as np
 
-from .diagnostics import waic as _waic
+from .diagnostics import waic as _waic, conditional_log_density as _cond_ld
 from .sampler import Hyper, Sampler, count_nonzero_columns
 
 
@@ -136,7 +136,8 @@ def local_state(state: dict, s0: int, gl: int) -> dict:
 def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hyper(),
                   init_draws=None, iter_draws=None, nranks=1, rank=0, device=0, comm_uid=None,
                   asm_batch=0, return_info=False, device_ingest=True, device_init=True, return_sd=False,
-                  n_components=0, rhs=None, probes=None, precision_probes=None, return_precision=False, loglik=False):
+                  n_components=0, rhs=None, probes=None, precision_probes=None, return_precision=False, loglik=False,
+                  predict=None):
     """Sigmaout = divideconquer(Y,g,k,BURNIN,MCMC,thin,rho)   (divideconquer.m:1).
 
     ``device_ingest`` (default): the zero-column scan and the partition/standardisation
@@ -206,6 +207,20 @@ def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hy
     "waic"}`` -- ll (S, n), logdet (S,) and ``diagnostics.waic(ll)`` (lppd, p_waic, elpd_waic, waic, se and the
     per-point terms) -- is appended after the ``precision_probes`` dict (if requested) and before info.
     Standardised units, as above; runs that are compared over g, k or rho must use the same Y.
+
+    ``predict``: ``(Ynew, observed)`` -- new rows Ynew, (nt, p_orig) or (p_orig,) with nt <= 32, in the data's
+    units and the input's column order, and a boolean mask ``observed`` (p_orig,), one for all rows: which
+    variables of the new rows are known.  The rows are centred and scaled with the training columns' mean
+    and standard deviation (dc:57-59; ``standardize_rows``), taken into Sigmaout's coordinates, and the
+    Gaussian conditional of the other variables given the observed ones is accumulated on the device over the
+    saved samples (Sampler.set_predict, capacity mcmc // thin; one rank only).  A dict ``{"mean",
+    "sd_between", "sd_total", "log_density", "lppd", "count"}`` is appended after the ``loglik`` dict (if
+    requested) and before info: mean (nt, p_orig) the posterior conditional mean in the data's units and the
+    input's column order, sd_between and sd_total (nt, p_orig) the between-sample and the total predictive
+    standard deviation (``unstandardize_prediction``), log_density (S, nt) the log density of each row's
+    observed part per saved sample and lppd (nt,) their log-mean-exp (``diagnostics.conditional_log_density``;
+    standardised units).  Entries of Ynew at unobserved positions are ignored.  A dropped all-zero column
+    counts as unobserved and gets mean 0 and sd 0.
     """
     t0 = time.perf_counter()                                     # dc:29 tic
     if device_ingest:
@@ -250,6 +265,11 @@ def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hy
             smp.set_precision_probes(permute_vectors(precision_probes, keep, init.varind))
         if loglik:
             smp.set_loglik()
+        if predict is not None:
+            Yraw = np.asarray(Y, dtype=np.float64)
+            cmean, csd = column_moments(Yraw)
+            Ystd, obs_in = standardize_rows(predict[0], predict[1], cmean, csd, keep, init.varind)
+            smp.set_predict(Ystd, obs_in)
         smp.run(1, N)                                            # dc:90-197
         Sigmaout = smp.get_sigma()
         Sigmasd = smp.get_sigma_moment("sd") if return_sd else None
@@ -271,6 +291,14 @@ def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hy
         if loglik:
             ll, _, ld = smp.loglik_draws(parts=True)
             llk = {"ll": ll, "logdet": ld, "waic": _waic(ll) if ll.shape[0] >= 2 else None}   # waic needs two samples
+        prd = None
+        if predict is not None:
+            pr = smp.predict()
+            prd = unstandardize_prediction(pr, cmean, csd, keep, init.varind, Yraw.shape[1])
+            cl = _cond_ld(pr["maha"], pr["logdet"], int(obs_in.sum())) if pr["count"] else None
+            prd["log_density"] = cl["per_sample"] if cl else np.zeros((0, Ystd.shape[1]))
+            prd["lppd"] = cl["lppd"] if cl else np.full(Ystd.shape[1], np.nan)
+            prd["count"] = pr["count"]
     finally:
         smp.close()
     elapsed = time.perf_counter() - t0                           # dc:200 toc
@@ -287,10 +315,55 @@ def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hy
         out += (prc,)
     if loglik:
         out += (llk,)
+    if predict is not None:
+        out += (prd,)
     if return_info:
         out += ({"varind": np.asarray(init.varind), "keep": keep, "n": n, "p": p, "P": P,
                  "K": K, "N": N, "seconds": elapsed},)
     return out if len(out) > 1 else out[0]
+
+
+def column_moments(Y):
+    """(mean, sd) of every input column of the training data Y (n x p_orig): the sample mean and the sample
+    standard deviation (ddof = 1) that dc:57-59 centres and scales with; an all-zero column has sd 0."""
+    Y = np.asarray(Y, dtype=np.float64)
+    return Y.mean(axis=0), Y.std(axis=0, ddof=1)
+
+
+def standardize_rows(Ynew, observed, mean, sd, keep, varind):
+    """New rows in the data's units into the coordinates the sweep works in.  Ynew is (nt, p_orig) or (p_orig,)
+    in the input's column order, observed a boolean (p_orig,) mask, mean and sd the training columns' moments
+    (``column_moments``).  Returns ``(Ystd, obs)``: Ystd (p, nt) = (Ynew - mean) / sd on the kept columns in
+    Sigmaout's order (``permute_vectors``), new rows as columns, zero at the unobserved positions (whatever
+    Ynew holds there, NaN included), and obs (p,) uint8.  Dropped all-zero columns fall away: they count as
+    unobserved."""
+    Yn = np.asarray(Ynew, dtype=np.float64)
+    Yn = Yn[None, :] if Yn.ndim == 1 else Yn
+    mean, sd = np.asarray(mean, dtype=np.float64), np.asarray(sd, dtype=np.float64)
+    ob = np.asarray(observed).astype(bool).reshape(-1)
+    if Yn.ndim != 2 or Yn.shape[1] != mean.size or ob.size != mean.size:
+        raise ValueError(f"Ynew must be (nt, {mean.size}) or ({mean.size},) and observed ({mean.size},), "
+                         f"got {Yn.shape} and {ob.shape}")
+    obs = permute_vectors(ob.astype(np.float64), keep, varind) != 0
+    cols = output_columns(keep, varind)
+    Ystd = np.zeros((cols.size, Yn.shape[0]))
+    Ystd[obs] = ((Yn[:, cols[obs]] - mean[cols[obs]]) / sd[cols[obs]]).T
+    return Ystd, obs.astype(np.uint8)
+
+
+def unstandardize_prediction(pred, mean, sd, keep, varind, p_orig) -> dict:
+    """``Sampler.predict()``'s mean, sd_between and sd_total ((p, nt), standardised, Sigmaout's order) in the
+    data's units and the input's column order, new rows as rows: mean (nt, p_orig) = mean_col + sd_col * yhat,
+    the standard deviations times sd_col.  Dropped all-zero columns get mean 0 and sd 0."""
+    mean, sd = np.asarray(mean, dtype=np.float64), np.asarray(sd, dtype=np.float64)
+    cols = output_columns(keep, varind)
+    out = {}
+    for f in ("mean", "sd_between", "sd_total"):
+        v = np.asarray(pred[f], dtype=np.float64) * sd[cols][:, None]
+        if f == "mean":
+            v = v + mean[cols][:, None]
+        out[f] = unpermute_vectors(v, keep, varind, p_orig).T.copy()
+    return out
 
 
 def truth_factors(Lam0, sig2, Y, keep, varind):

@@ -480,6 +480,68 @@ class Sampler:
         ll = -0.5 * (self.P * self.g * np.log(2.0 * np.pi) + ld[:, None] + maha)
         return (ll, maha, ld) if parts else ll
 
+    # -- conditional prediction of unobserved variables --------------------------------
+    def set_predict(self, Ynew, observed, capacity=None):
+        """Predict the unobserved variables of new rows from their observed ones under every saved sample of
+        later runs (dcfm_set_predict).  ``Ynew`` is (p,) or (p, nt), 0 <= nt <= 32 new rows as columns, in
+        Sigmaout's permuted, standardised coordinates; ``observed`` is a (p,) mask, nonzero = observed, one
+        mask for all rows; entries of Ynew at unobserved positions are ignored (NaN included).  ``Ynew=None``
+        (or a (p, 0) block) accumulates the conditional variance and log det Sigma_AA(s) alone.  Up to
+        ``capacity`` samples are accumulated (default ``mcmc // thin``); later saved samples are ignored.
+        Calling it again replaces the inputs and zeroes the accumulators; ``set_predict(None, None, 0)``
+        turns it off and frees its buffers.  One rank only: a sampler with a communicator raises
+        DcfmError (DCFM_ERR_UNSUPPORTED).  Independent of the probes, precision probes and log-likelihood."""
+        p = self.P * self.g
+        if capacity is None:
+            capacity = int(self.cfg.mcmc) // int(self.cfg.thin)
+        if observed is None:
+            if int(capacity) != 0:
+                raise ValueError("observed is required unless capacity == 0")
+            self._check(self.lib.dcfm_set_predict(self.h, None, None, 0, 0))
+            self._pred_nt = self._pred_cap = 0
+            return
+        obs = np.ascontiguousarray(np.asarray(observed) != 0, dtype=np.uint8)
+        if obs.shape != (p,):
+            raise ValueError(f"observed must be ({p},), got {obs.shape}")
+        Y = np.zeros((p, 0)) if Ynew is None else np.asarray(Ynew, dtype=np.float64)
+        if Y.ndim not in (1, 2) or Y.shape[0] != p:
+            raise ValueError(f"Ynew must be (p,) or (p, nt) with p = {p}, got {Y.shape}")
+        Y2 = _f64F(Y.reshape(p, -1) if Y.ndim == 1 else Y)
+        self._check(self.lib.dcfm_set_predict(self.h, _ptr(Y2) if Y2.shape[1] else None,
+                                              obs.ctypes.data_as(C.POINTER(C.c_uint8)), Y2.shape[1], int(capacity)))
+        self._pred_nt = Y2.shape[1] if int(capacity) > 0 else 0
+        self._pred_cap = int(capacity)
+
+    def predict_raw(self):
+        """``(mean, m2, cvar, maha, logdet, count)`` exactly as dcfm_get_predict returns them: mean and m2
+        (p, nt), cvar (p,), maha (count, nt), logdet (count,)."""
+        nt, cap = getattr(self, "_pred_nt", 0), getattr(self, "_pred_cap", 0)
+        p = self.P * self.g
+        cnt = C.c_int64(0)
+        mean = np.zeros((p, nt), dtype=np.float64, order="F")
+        m2 = np.zeros((p, nt), dtype=np.float64, order="F")
+        cvar = np.zeros(p, dtype=np.float64)
+        maha = np.zeros((max(cap, 1), nt), dtype=np.float64)
+        ld = np.zeros(max(cap, 1), dtype=np.float64)
+        self._check(self.lib.dcfm_get_predict(self.h, _ptr(mean), _ptr(m2), _ptr(cvar), _ptr(maha), _ptr(ld),
+                                              C.byref(cnt)))
+        S = int(cnt.value)
+        return mean, m2, cvar, maha[:S].copy(), ld[:S].copy(), S
+
+    def predict(self) -> dict:
+        """The conditional prediction accumulated so far, in standardised, permuted coordinates: ``mean``
+        (p, nt) = avg_s E[y_j | y_A, Sigma(s)] (on an observed row: of the noise-free signal), ``sd_between``
+        (p, nt) the standard deviation of that conditional mean over the samples, ``cvar`` (p,) = avg_s
+        Var[y_j | y_A, Sigma(s)], ``sd_total`` (p, nt) = sqrt(cvar + var_between) (the law of total
+        variance; the between-sample variance m2 - mean^2 clamped at 0), ``maha`` (count, nt) =
+        y_A' Sigma_AA(s)^-1 y_A and ``logdet`` (count,) = log det Sigma_AA(s) per sample (the input of
+        ``diagnostics.conditional_log_density``), and ``count``, the samples accumulated (the divisor).
+        count 0 and empty draws when nothing is set or nothing was saved yet."""
+        mean, m2, cvar, maha, ld, S = self.predict_raw()
+        vb = np.maximum(m2 - mean * mean, 0.0)
+        return {"mean": mean, "sd_between": np.sqrt(vb), "cvar": cvar, "sd_total": np.sqrt(cvar[:, None] + vb),
+                "maha": maha, "logdet": ld, "count": S}
+
     # -- measurement -----------------------------------------------------------------
     def set_profiling(self, on: bool):
         self._check(self.lib.dcfm_set_profiling(self.h, 1 if on else 0))

@@ -444,6 +444,56 @@ int  dcfm_get_precision_draws(dcfm_handle *h, double *Q, double *logdet, int64_t
 int  dcfm_set_loglik(dcfm_handle *h, int64_t capacity);
 int  dcfm_get_loglik(dcfm_handle *h, double *maha, double *logdet, int64_t *count);
 
+/* ---- conditional prediction of unobserved variables (imputation, nowcasting, partly observed held-out rows) ----
+ * A new row arrives with the variables of an index set A observed.  Under the posterior, what are the others and
+ * how sure are we?  For every saved sample s the device forms, for every variable j and new row t,
+ *   yhat_jt(s) = E[(Lambda eta)_j | y_A, Sigma(s)]  (for j outside A this is E[y_j | y_A, Sigma(s)]),
+ *   cv_j(s)    = the predictive variance of a fresh observation of variable j given y_A (for j outside A this is
+ *                Var[y_j | y_A, Sigma(s)]),
+ *   q_t(s) = y_A' Sigma_AA(s)^{-1} y_A  and  log det Sigma_AA(s),
+ * and accumulates sum yhat, sum yhat^2 and sum cv over the samples.  Restricting to A only removes rows from the
+ * weighted Gram of the precision draws, so Sigma_AA(s) is again block-diagonal plus rank K: the K x K stage is the
+ * precision draws' kernel with the weight masked, everything p-sized is one more fp64-MFMA pass over Lambda, and
+ * there is no branch on the mask after the Gram (csrc/predict.hip has the recursion and the launch chain).
+ * The posterior answer follows by the law of total variance: mean_jt = avg_s yhat_jt(s) and
+ * Var[y_j | y_A] = avg_s cv_j(s) + var_s yhat_jt(s) = cvar_j + (m2_jt - mean_jt^2).
+ *
+ * dcfm_set_predict: Ynew is p x nt column-major in Sigmaout's permuted, standardised coordinates, 0 <= nt <= 32
+ * new rows as columns; observed is p bytes, nonzero = observed, one mask for all nt rows.  With nt == 0 (Ynew may
+ * be NULL) only cvar and log det Sigma_AA(s) are produced.  Entries of Ynew at unobserved positions are ignored,
+ * NaN included (they are masked when copied in, never by a product).  From the next dcfm_run on every saved sample
+ * is accumulated and its draw recorded until `capacity` samples are held; later saved samples are ignored, so the
+ * accumulators and the draws always cover the same samples.  A second call replaces the inputs and zeroes the
+ * accumulators and the count; capacity == 0 turns the feature off and frees its buffers; nothing is allocated or
+ * launched until a call with capacity > 0.  Booked under DCFM_K_SAVE.  No floating-point atomics, fixed summation
+ * orders, one sample added per launch in sample order: the same inputs give the same bits, in one dcfm_run call
+ * or one iteration per call.  Independent of dcfm_set_probes, dcfm_set_precision_probes and dcfm_set_loglik: all
+ * may be on at once and none changes another's bits.
+ * One rank only: the closing step of Sigma_AA(s) needs the sum over ALL shards of H_m and F_m on the device at
+ * save time, one more all-gather per saved sample that the sweep does not have.  On a handle of the collective
+ * path (nranks > 1 or DCFM_FLAG_COMM_SELF) a call with capacity > 0 is DCFM_ERR_UNSUPPORTED, whether it comes
+ * before or after dcfm_comm_init*, and nothing is set.
+ * Device bytes: 8 (P g (3 nt + 1) + K^2 + nt^2 + 1 + g (4 K^2 + 2 K nt) + g K4 (ntp + Kp) + capacity (nt + 1) +
+ * scratch) + P g, with K4 = K rounded up to 4, ntp = nt and Kp = K rounded up to 16: the new rows, the three
+ * accumulators, S^{-1}, the sample's [q | ld], the K x K products and the coefficients [t_m | I - M_m] of the
+ * shards, the draws, the mask; scratch = that of dcfm_set_precision_probes at nv = nt.  LDS: the K x K stages up
+ * to 8 (K^2 + 16 K) bytes + 2 KiB (146 KiB at K = 128), the pass over Lambda 256 (K4 + Kp + 2) bytes (66 KiB at K = 128).
+ * Errors (DCFM_ERR_INVALID, the setting made before stays as it was): NULL handle ("null handle"), NULL observed
+ * with capacity > 0 or NULL Ynew with nt > 0 and capacity > 0 ("null argument"), nt outside 0..32, capacity < 0, a
+ * non-finite entry of Ynew at an observed position.
+ *
+ * dcfm_get_predict: count (required) receives the number of samples accumulated; every other output is nullable.
+ * mean and m2 are p x nt column-major: sum yhat / count and sum yhat^2 / count (count is the number of samples
+ * actually accumulated, the population form, not effsamp); cvar has p entries, sum cv / count; maha is nt x
+ * count column-major, q_t of sample s at maha[s * nt + t]; logdet has count entries.  Blocks (synchronises the
+ * sweep stream) and does not disturb a later dcfm_run.  With nothing set *count = 0 and DCFM_OK.  After a run that
+ * ended in DCFM_ERR_NUMERIC it returns what the device holds: a NaN state gives NaN outputs (no stage takes a
+ * data-dependent trip count).  Errors (DCFM_ERR_INVALID): NULL handle ("null handle"), NULL count ("null
+ * argument"). */
+int  dcfm_set_predict(dcfm_handle *h, const double *Ynew, const uint8_t *observed, int32_t nt, int64_t capacity);
+int  dcfm_get_predict(dcfm_handle *h, double *mean, double *m2, double *cvar, double *maha, double *logdet,
+                      int64_t *count);
+
 /* ---- measurement --------------------------------------------------------- */
 /* Per-kernel HIP-event timing on the handle's stream (off by default).
  * Kernel ids: DCFM_K_* below.  Times are accumulated device milliseconds. */

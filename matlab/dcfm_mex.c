@@ -51,6 +51,16 @@
  *                                         runs; capacity as for 'set_probes'; independent of both
  *   [maha, logdet] = dcfm_mex('loglik', h)   the recorded draws, n x S and S x 1 (n x 0 and 0 x 1 with nothing
  *                                         set); log N(y_i; 0, Sigma_s) = -(p*log(2*pi) + logdet(s) + maha(i,s))/2
+ *   dcfm_mex('set_predict', h, Ynew, observed[, capacity])   predict the unobserved variables of nt new rows
+ *                                         (the columns of Ynew, p x nt, 0 <= nt <= 32, Sigmaout's standardised
+ *                                         coordinates) from the observed ones (observed p x 1 double, nonzero =
+ *                                         observed; entries of Ynew elsewhere are ignored) under every saved sample
+ *                                         of later runs; capacity as for 'set_probes'; one rank only
+ *   [mean, m2, cvar, maha, logdet] = dcfm_mex('predict', h)   the accumulated prediction: mean and m2 p x nt (the
+ *                                         averages of the conditional mean and of its square), cvar p x 1 (the
+ *                                         average conditional variance; total variance cvar + m2 - mean.^2), maha
+ *                                         nt x S = y_A' * inv(Sigma_AA_s) * y_A and logdet S x 1 (empty with
+ *                                         nothing set)
  *   e = dcfm_mex('error', h, U, s, iters)[||S-S0||_F, ||S0||_F, ||S-S0||_2] vs S0 = UU' + diag(s)
  *   dcfm_mex('set_trace', h, cap); T = dcfm_mex('get_trace', h)     chain trace (count x 4)
  *   dcfm_mex('destroy', h)
@@ -72,6 +82,7 @@ typedef struct {
     int64_t mcmc, thin;        /* default capacity of 'set_probes' */
     int64_t nv;                /* width of the probe block the library holds (0: none) */
     int64_t pnv;               /* width of the precision-probe block the library holds */
+    int64_t pnt;               /* new rows of the prediction the library holds */
 } slot;
 static slot S[NSLOT];          /* handles live across calls */
 
@@ -144,7 +155,7 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
             mexErrMsgIdAndTxt("dcfm:create", "%s", dcfm_last_error(NULL));
         }
         S[i].n = c.n; S[i].P = c.P; S[i].g = c.g; S[i].K = c.K;
-        S[i].mcmc = c.mcmc; S[i].thin = c.thin; S[i].nv = 0; S[i].pnv = 0;
+        S[i].mcmc = c.mcmc; S[i].thin = c.thin; S[i].nv = 0; S[i].pnv = 0; S[i].pnt = 0;
         mexLock();
         plhs[0] = mxCreateDoubleScalar(i);
     } else if (!strcmp(cmd, "set_data")) {
@@ -471,6 +482,53 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         plhs[0] = q;
         if (nlhs > 1) plhs[1] = ld;
         else mxDestroyArray(ld);
+    } else if (!strcmp(cmd, "set_predict")) {        /* dcfm_mex('set_predict', h, Ynew, observed[, capacity]) */
+        if (nrhs != 4 && nrhs != 5)
+            mexErrMsgIdAndTxt("dcfm:nargs", "'%s' takes 3 or 4 arguments, got %d", cmd, nrhs - 1);
+        /* the argument that needs no handle first: a malformed call never reaches the library */
+        const double cap = nrhs > 4 ? scalar(prhs[4], "capacity") : -1;
+        if (nrhs > 4 && (cap < 0 || cap > 9007199254740992.0 || cap != (double)(int64_t)cap))
+            mexErrMsgIdAndTxt("dcfm:arg", "capacity must be a non-negative integer");
+        slot *t = get(prhs[1]);
+        const int64_t p = t->P * t->g;               /* the row count the library reads */
+        const int64_t capacity = nrhs > 4 ? (int64_t)cap : (t->thin > 0 ? t->mcmc / t->thin : 0);
+        const mxArray *Y = prhs[2], *ob = prhs[3];
+        if (capacity > 0 && (!mxIsDouble(Y) || mxIsComplex(Y) || (int64_t)mxGetM(Y) != p || mxGetN(Y) > 32 ||
+                             (int64_t)mxGetNumberOfElements(Y) != p * (int64_t)mxGetN(Y)))
+            mexErrMsgIdAndTxt("dcfm:arg", "Ynew must be a real double p x nt matrix, p = %lld, 0 <= nt <= 32", (long long)p);
+        if (capacity > 0 && (!mxIsDouble(ob) || mxIsComplex(ob) || (int64_t)mxGetNumberOfElements(ob) != p))
+            mexErrMsgIdAndTxt("dcfm:arg", "observed must be a real double vector of p = %lld elements", (long long)p);
+        if (capacity > 0) {
+            const int32_t nt = (int32_t)mxGetN(Y);
+            uint8_t *mask = (uint8_t *)mxMalloc((mwSize)p);
+            const double *od = mxGetDoubles(ob);
+            for (int64_t j = 0; j < p; ++j) mask[j] = od[j] != 0.0;
+            const int rc = dcfm_set_predict(t->h, nt > 0 ? mxGetDoubles(Y) : NULL, mask, nt, capacity);
+            mxFree(mask);
+            ck(t->h, rc);
+            t->pnt = nt;
+        } else {
+            ck(t->h, dcfm_set_predict(t->h, NULL, NULL, 0, 0));
+            t->pnt = 0;
+        }
+    } else if (!strcmp(cmd, "predict")) {            /* [mean, m2, cvar, maha, logdet] = dcfm_mex('predict', h) */
+        nargs(nrhs, 2, cmd);
+        slot *t = get(prhs[1]);
+        int64_t cnt = 0;
+        ck(t->h, dcfm_get_predict(t->h, NULL, NULL, NULL, NULL, NULL, &cnt));
+        const mwSize p = (mwSize)(t->P * t->g), nt = (mwSize)(cnt > 0 ? t->pnt : 0);
+        mxArray *o[5];                               /* the sizes the library writes */
+        o[0] = mxCreateDoubleMatrix(p, nt, mxREAL);
+        o[1] = mxCreateDoubleMatrix(p, nt, mxREAL);
+        o[2] = mxCreateDoubleMatrix(cnt > 0 ? p : 0, cnt > 0 ? 1 : 0, mxREAL);
+        o[3] = mxCreateDoubleMatrix(nt, (mwSize)cnt, mxREAL);
+        o[4] = mxCreateDoubleMatrix((mwSize)cnt, 1, mxREAL);
+        if (cnt > 0)
+            ck(t->h, dcfm_get_predict(t->h, nt > 0 ? mxGetDoubles(o[0]) : NULL, nt > 0 ? mxGetDoubles(o[1]) : NULL,
+                                      mxGetDoubles(o[2]), nt > 0 ? mxGetDoubles(o[3]) : NULL, mxGetDoubles(o[4]), &cnt));
+        for (int i = 0; i < 5; ++i)
+            if (i == 0 || i < nlhs) plhs[i] = o[i];
+            else mxDestroyArray(o[i]);
     } else if (!strcmp(cmd, "destroy")) {
         nargs(nrhs, 2, cmd);
         slot *t = get(prhs[1]);

@@ -14,8 +14,10 @@ from .sampler import Hyper, Sampler, rng_fill, count_nonzero_columns, STATE_FIEL
 from . import diagnostics
 from .diagnostics import heldout_log_density, summarize_probes, partial_correlations, waic, conditional_log_density
 from .driver import divideconquer, preprocess, preprocess_device, shard_columns, partition_standardize, initial_state, local_state, truth_factors, output_columns, unpermute_sigma, unpermute_vectors, permute_vectors, unpermute_precision
+from .driver import preprocess_missing, partition_standardize_missing, observed_moments, unstandardize_imputation
 
 __all__ = [
+    "preprocess_missing", "partition_standardize_missing", "observed_moments", "unstandardize_imputation",
     "DcfmError", "load_library", "EXPORTS", "LIB_PATH", "Hyper", "Sampler", "rng_fill",
     "STATE_FIELDS", "divideconquer", "preprocess", "partition_standardize", "initial_state",
     "local_state", "truth_factors", "output_columns", "unpermute_sigma", "count_nonzero_columns",

@@ -55,6 +55,7 @@ EXPORTS = (
     "dcfm_sigma_solve", "dcfm_set_probes", "dcfm_get_probe_draws", "dcfm_set_precision_probes",
     "dcfm_get_precision_draws", "dcfm_get_precision_mean_cols", "dcfm_get_precision_mean",
     "dcfm_set_loglik", "dcfm_get_loglik", "dcfm_set_predict", "dcfm_get_predict",
+    "dcfm_set_missing", "dcfm_get_imputed",
 )
 
 
@@ -140,6 +141,8 @@ def load_library(path: Path | None = None):
         "dcfm_get_loglik": (C.c_int, [vp, _DP, _DP, C.POINTER(C.c_int64)]),
         "dcfm_set_predict": (C.c_int, [vp, _DP, C.POINTER(C.c_uint8), C.c_int32, C.c_int64]),
         "dcfm_get_predict": (C.c_int, [vp, _DP, _DP, _DP, _DP, _DP, C.POINTER(C.c_int64)]),
+        "dcfm_set_missing": (C.c_int, [vp, C.POINTER(C.c_uint8), C.c_int64]),
+        "dcfm_get_imputed": (C.c_int, [vp, _DP, _DP, _DP, C.POINTER(C.c_int64)]),
         "dcfm_set_profiling": (C.c_int, [vp, C.c_int]),
         "dcfm_set_profiling_mask": (C.c_int, [vp, C.c_uint32]),
         "dcfm_set_profiling_stride": (C.c_int, [vp, C.c_int32]),

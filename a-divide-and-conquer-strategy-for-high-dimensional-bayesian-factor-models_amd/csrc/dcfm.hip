@@ -366,6 +366,7 @@ void dcfm_destroy(dcfm_handle *h) {
     if (h->prec_mem) (void)hipFree(h->prec_mem);
     if (h->ll_mem) (void)hipFree(h->ll_mem);
     if (h->pred_mem) (void)hipFree(h->pred_mem);
+    if (h->imp_mem) (void)hipFree(h->imp_mem);
     if (h->sasm && h->sasm != h->stream) (void)hipStreamDestroy(h->sasm);
     if (h->side && h->side != h->stream) (void)hipStreamDestroy(h->side);
     if (h->sdraw && h->sdraw != h->stream) (void)hipStreamDestroy(h->sdraw);
@@ -474,7 +475,8 @@ static int open_batch(dcfm_handle *h) {
     return DCFM_OK;
 }
 
-// the loading rows (k_lambda) and dc:169's direct residual where it is asked for.  Launch chain of a
+// the loading rows (k_lambda) and dc:169's direct residual where it is asked for, then the imputation step of
+// dcfm_set_missing (the iteration's X, Z, Lambda and ps are final behind them).  Launch chain of a
 // saved iteration, K <= 32: [wait e_free of a batch's first sample] k_lambda (writes the sample into
 // slot h->batch of Lb / wsum / wslot [h->lb]) -> save_sample: probes, the batch count, the flush of a full
 // batch behind it.  Exact residual and K > 32: k_lambda, k_resid / k_resid_flagged, then k_save.
@@ -503,6 +505,12 @@ static int loading_rows(dcfm_handle *h, const DrawsDev &dr, int64_t it, bool lam
         launch_resid_flagged(d, b, dr, it, s);
     }
     h->plam_valid = false;
+    if (h->imp.nmiss) {                               // dcfm_set_missing: X, Z, Lambda, ps of it are final
+        KTimer t(h, DCFM_K_SAVE, s);
+        const bool acc = saved_iteration(h, it) && h->imp_n < h->imp_cap;
+        launch_impute(d, b, h->imp, it, acc, s);
+        if (acc) h->imp_n += 1;
+    }
     return DCFM_OK;
 }
 

@@ -217,6 +217,17 @@ struct Predict {
     double *sinv, *qd, *work, *coef, *sum, *sum2, *cvsum, *draws;
     int T, Tp, wc;
 };
+// Missing training data (impute.hip, dcfm_set_missing; nmiss == 0 when off).  The nmiss missing entries of this
+// rank's shards are listed twice: as entries e sorted by (local shard, row i, column j) -- row[e] = i, col[e] = m PP + j
+// (the index into yy / ps), perm[e] = the entry's place in the second order -- and as vcsc, their current values
+// sorted by (local shard, column, row), where column c of the ncol columns with a missing entry (cols[c] = m PP + j)
+// owns vcsc[colptr[c] .. colptr[c + 1]).  yyobs [ncol] = the sum of squares of a column's observed entries.  The
+// accumulators of dcfm_get_imputed (null with capacity 0): smu, smu2 [nmiss] in entry order, snv [ncol]
+struct Impute {
+    int nmiss, ncol;
+    const int *row, *col, *perm, *colptr, *cols;
+    double *vcsc, *yyobs, *smu, *smu2, *snv;
+};
 // Precision mean (precision_mean.hip, DCFM_FLAG_PRECISION_MEAN; all null when off).  Kept out of Bufs, which
 // the sweep's kernels take by value: Prec the accumulator (laid out as Bufs::Sigma), pfac the factor panels of
 // a flush, pscr the K x K scratch, KH the columns of a quarter of pfac (B K rounded up to ASM_KC)
@@ -375,6 +386,9 @@ void launch_precision_masked(const Dims &d, const Bufs &b, const Precision &pr, 
                              double *draw, hipStream_t st);
 // predict.hip: sample s of the conditional prediction from the current Lambda, omega (same place, one rank)
 void launch_predict(const Dims &d, const Bufs &b, const Predict &pd, int64_t s, hipStream_t st);
+// impute.hip: the data-augmentation step of iteration iter from the final X, Z, Lambda, ps (k_impute: the missing
+// entries of Y and vcsc redrawn; k_impute_yy: yy of their columns); acc: also one sample into the accumulators
+void launch_impute(const Dims &d, const Bufs &b, const Impute &im, int64_t iter, bool acc, hipStream_t s);
 // loglik.hip: draw s of the rows' y_i' Sigma^{-1} y_i and log det Sigma from the current Lambda, omega (same place)
 void launch_loglik(const Dims &d, const Bufs &b, const LogLik &ll, int64_t s, hipStream_t st);
 // init.hip: dc:68-87 initial state from Philox (iteration-0 counters), delta/tau buffer 0

@@ -88,6 +88,11 @@ struct dcfm_handle {
     double *pred_mem = nullptr;
     Predict pred{};
     int64_t pred_cap = 0, pred_n = 0;
+    // missing training data (dcfm_set_missing, impute.hip): one allocation, null when off; imp_cap / imp_n the
+    // saved samples the accumulators may hold / hold
+    void *imp_mem = nullptr;
+    Impute imp{};
+    int64_t imp_cap = 0, imp_n = 0;
     // posterior mean of the precision matrix (DCFM_FLAG_PRECISION_MEAN, precision_mean.hip): null when off
     PrecMean pm{};
     bool prof = false;
@@ -195,6 +200,9 @@ inline int numeric_status(dcfm_handle *h) {
                                          "after dcfm_run; set_state / init_state to restart");
     return DCFM_OK;
 }
+
+// impute.hip: forget the mask (dcfm_set_data*: it belongs to the data that is being replaced)
+void impute_drop(dcfm_handle *h);
 
 // host generator of the seeded Krylov starts (dcfm_sigma_error, dcfm_sigma_eigs)
 inline uint64_t splitmix64(uint64_t &x) {

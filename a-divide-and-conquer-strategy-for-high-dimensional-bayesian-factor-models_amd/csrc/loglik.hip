@@ -351,6 +351,10 @@ int dcfm_set_loglik(dcfm_handle *h, int64_t capacity) {
     if (!h) return fail(h, DCFM_ERR_INVALID, "null handle");
     const Dims &d = h->d;
     if (capacity < 0) return fail(h, DCFM_ERR_INVALID, "set_loglik: capacity %lld < 0", (long long)capacity);
+    // with a mask the rows the pass reads are completed by the current draw: that is the completed-data likelihood
+    if (capacity > 0 && h->imp.nmiss)
+        return fail(h, DCFM_ERR_UNSUPPORTED, "set_loglik: the handle has missing data (dcfm_set_missing); the rows' "
+                                             "likelihood would be that of the completed data, not of the observed entries");
     HIPC(h, hipSetDevice(h->cfg.device));
     HIPC(h, hipStreamSynchronize(h->stream));
     LogLik ll{};

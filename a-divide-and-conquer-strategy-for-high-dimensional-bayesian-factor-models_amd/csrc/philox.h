@@ -35,6 +35,7 @@ enum RngSite : uint32_t {
     SITE_INIT_Z = 10,     // dc:80  N(0,1)     n x K x g
     SITE_INIT_D1 = 11,    // dc:83  Ga(ad1)    delta(1,:,m)
     SITE_INIT_D2 = 12,    // dc:83  Ga(ad2)    delta(2:K,:,m)
+    SITE_IMPUTE = 13,     // the missing entries of Y  N(0,1)  n x P x g  (row j, index i; dcfm_set_missing)
     SITE_DIAG = 15,  // dcfm_rng_fill
 };
 

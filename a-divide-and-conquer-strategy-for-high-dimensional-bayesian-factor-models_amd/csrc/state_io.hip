@@ -15,6 +15,7 @@ int dcfm_set_data(dcfm_handle *h, const double *Yd) {
     if (!h || !Yd) return fail(h, DCFM_ERR_INVALID, "null argument");
     const Dims &d = h->d;
     HIPC(h, hipSetDevice(h->cfg.device));
+    impute_drop(h);   // dcfm_set_missing's mask belongs to the data it was given for
     std::vector<double> buf((size_t)d.NP * d.PP, 0.0);
     std::vector<double> yy((size_t)d.G * d.PP, 0.0);
     for (int m = 0; m < d.G; ++m) {
@@ -59,6 +60,7 @@ int dcfm_set_data_raw(dcfm_handle *h, const double *Y, int64_t p_in, const int64
             return fail(h, DCFM_ERR_INVALID, "set_data_raw: cols[%lld] = %lld outside [0, %lld)", (long long)c,
                         (long long)cols[c], (long long)p_in);
     HIPC(h, hipSetDevice(h->cfg.device));
+    impute_drop(h);   // as dcfm_set_data
     DevScratch sc;
     void *qY = nullptr, *qc = nullptr, *qsd = nullptr, *qbad = nullptr, *qmi = nullptr;
     const size_t ybytes = (size_t)d.n * (size_t)p_in * sizeof(double);

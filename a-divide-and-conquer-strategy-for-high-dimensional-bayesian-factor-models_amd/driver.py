@@ -77,6 +77,74 @@ def partition_standardize(Y, g, varind):
     return (Yd - Md) * (1.0 / np.sqrt(VYd))
 
 
+def preprocess_missing(Y, g, k):
+    """dc:29-41 for data with holes (``divideconquer(..., impute=True)``): NaN marks a missing entry and the
+    zero-column scan ignores it, so a column whose observed entries are all zero (or that has none) is dropped.
+    Returns (Y_kept, n, p, P, K, keep) as ``preprocess``; Y_kept keeps its NaNs."""
+    Y = np.asarray(Y, dtype=np.float64)
+    if Y.ndim != 2:
+        raise ValueError("Y must be n x p (rows are observations, dc:30)")
+    n = Y.shape[0]
+    keep = np.flatnonzero(np.count_nonzero(np.where(np.isnan(Y), 0.0, Y), axis=0) != 0)
+    p = keep.size
+    if g < 1 or p % g or k % g:
+        raise ValueError(f"P = p/g = {p}/{g} and K = k/g = {k}/{g} must be integers (dc:41)")
+    return Y[:, keep], n, p, p // g, k // g, keep
+
+
+def partition_standardize_missing(Y, g, varind):
+    """dc:48-59 on the observed entries: the partition of ``partition_standardize``, every column centred with the
+    mean and scaled with the sample standard deviation (ddof = 1) of its observed entries.  Returns ``(Yd, mask)``,
+    both n x P x g: the missing entries of Yd are 0 (the standardised column mean) and mask marks them.  A column
+    with fewer than two observed entries or zero observed variance raises ValueError."""
+    n, p = Y.shape
+    P = p // g
+    Yd = np.empty((n, P, g))
+    for m in range(g):
+        Yd[:, :, m] = Y[:, varind[m * P:(m + 1) * P]]
+    mask = np.isnan(Yd)
+    nobs = n - mask.sum(axis=0, keepdims=True)
+    if np.any(nobs < 2):
+        raise ValueError("a column has fewer than two observed entries: its variance (dc:57) is undefined")
+    tot = np.where(mask, 0.0, Yd).sum(axis=0, keepdims=True)
+    Md = tot / nobs
+    dev = np.where(mask, 0.0, Yd - Md)
+    VYd = (dev * dev).sum(axis=0, keepdims=True) / (nobs - 1)
+    if np.any(VYd == 0):
+        raise ValueError("a column's observed entries are constant: zero variance (dc:59 would divide by zero, Q13)")
+    return dev * (1.0 / np.sqrt(VYd)), mask
+
+
+def observed_moments(Y):
+    """``column_moments`` on the observed (non-NaN) entries: (mean, sd) of every input column, ddof = 1; a column
+    with fewer than two observed entries gets sd 0, one with none mean 0."""
+    Y = np.asarray(Y, dtype=np.float64)
+    mask = np.isnan(Y)
+    nobs = Y.shape[0] - mask.sum(axis=0)
+    mean = np.where(mask, 0.0, Y).sum(axis=0) / np.maximum(nobs, 1)
+    dev = np.where(mask, 0.0, Y - mean)
+    return mean, np.sqrt((dev * dev).sum(axis=0) / np.maximum(nobs - 1, 1)) * (nobs > 1)
+
+
+def unstandardize_imputation(imp, Y, mean, sd, keep, varind, s0=0) -> dict:
+    """``Sampler.imputed()`` of the shards [s0, s0 + g_local) in the data's units and the input's column order:
+    ``mean`` (n, p_orig) is Y with its NaNs replaced by mean_col + sd_col * (posterior mean), ``sd`` (n, p_orig) the
+    total predictive standard deviation times sd_col, 0 at observed entries.  Missing entries of dropped all-zero
+    columns come back 0 with sd 0; those of other ranks' shards stay NaN."""
+    Y = np.asarray(Y, dtype=np.float64)
+    mean, sd = np.asarray(mean, dtype=np.float64), np.asarray(sd, dtype=np.float64)
+    n, P, gl = imp["mean"].shape
+    cols = output_columns(keep, varind)[s0 * P:(s0 + gl) * P]
+    out_mean, out_sd = Y.copy(), np.zeros(Y.shape)
+    dropped = np.setdiff1d(np.arange(Y.shape[1]), np.asarray(keep))
+    out_mean[:, dropped] = np.where(np.isnan(Y[:, dropped]), 0.0, Y[:, dropped])
+    mk = imp["mask"].reshape(n, P * gl, order="F")
+    mu = mean[cols] + sd[cols] * imp["mean"].reshape(n, P * gl, order="F")
+    out_mean[:, cols] = np.where(mk, mu, Y[:, cols])
+    out_sd[:, cols] = np.where(mk, sd[cols] * imp["sd_total"].reshape(n, P * gl, order="F"), 0.0)
+    return {"mean": out_mean, "sd": out_sd, "count": imp["count"]}
+
+
 class _HostInitDraws:
     """Standard variates for dc:50-83 from NumPy (the reference uses MATLAB's stream)."""
 
@@ -137,7 +205,7 @@ def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hy
                   init_draws=None, iter_draws=None, nranks=1, rank=0, device=0, comm_uid=None,
                   asm_batch=0, return_info=False, device_ingest=True, device_init=True, return_sd=False,
                   n_components=0, rhs=None, probes=None, precision_probes=None, return_precision=False, loglik=False,
-                  predict=None):
+                  predict=None, impute=False):
     """Sigmaout = divideconquer(Y,g,k,BURNIN,MCMC,thin,rho)   (divideconquer.m:1).
 
     ``device_ingest`` (default): the zero-column scan and the partition/standardisation
@@ -221,9 +289,30 @@ def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hy
     observed part per saved sample and lppd (nt,) their log-mean-exp (``diagnostics.conditional_log_density``;
     standardised units).  Entries of Ynew at unobserved positions are ignored.  A dropped all-zero column
     counts as unobserved and gets mean 0 and sd 0.
+
+    ``impute``: with True the NaN entries of Y are missing training data (without it a NaN is handled exactly as
+    before: it runs through the sweep and ends the chain in DCFM_ERR_NUMERIC).  dc:31-59 then run on the host
+    whatever ``device_ingest`` says: the zero-column scan ignores NaN (``preprocess_missing``), every column is
+    centred and scaled with the mean and sample standard deviation of its observed entries
+    (``partition_standardize_missing``; a kept column with fewer than two observed entries or zero observed
+    variance raises ValueError), and the missing entries are uploaded as 0 together with their mask
+    (Sampler.set_missing, capacity mcmc // thin): every iteration then redraws them on the device from their
+    conditional given eta, Lambda and ps.  A dict ``{"mean", "sd", "count"}`` is appended after the ``predict``
+    dict (if requested) and before info: mean (n, p_orig) is the input with its NaNs replaced by the posterior
+    mean in the data's units, sd (n, p_orig) the total predictive standard deviation in the data's units, 0 at
+    observed entries (``unstandardize_imputation``).  Missing entries of dropped all-zero columns come back 0
+    with sd 0; with several ranks every rank fills in the entries of its own shards.  With ``predict`` the
+    training moments used for the new rows are the observed-entry ones.  Not together with ``loglik``
+    (ValueError): that would be the likelihood of the completed data.
     """
     t0 = time.perf_counter()                                     # dc:29 tic
-    if device_ingest:
+    if impute and loglik:
+        raise ValueError("impute=True with loglik=True: the rows' log-likelihood would be that of the completed "
+                         "data, not of the observed entries")
+    if impute:
+        device_ingest = False
+        Yk, n, p, P, K, keep = preprocess_missing(Y, g, k)
+    elif device_ingest:
         Y = np.asarray(Y, dtype=np.float64)
         n, p, P, K, keep = preprocess_device(Y, g, k, device=device)
     else:
@@ -236,7 +325,9 @@ def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hy
         init = _HostVarind(seed, p)
     else:
         init = _HostInitDraws(seed, n, p, g, K, hyper)
-    if not device_ingest:
+    if impute:
+        Yd, miss = partition_standardize_missing(Yk, g, np.asarray(init.varind))
+    elif not device_ingest:
         Yd = partition_standardize(Yk, g, np.asarray(init.varind))
     state = None if on_device_init else initial_state(n, P, K, g, rho, hyper, init)
     gl = g // nranks
@@ -253,6 +344,8 @@ def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hy
             smp.set_data_raw(Y, shard_columns(keep, init.varind, P, s0, gl))
         else:
             smp.set_data(Yd[:, :, s0:s0 + gl])
+        if impute:
+            smp.set_missing(miss[:, :, s0:s0 + gl])
         if state is None:
             smp.init_state()
         else:
@@ -267,7 +360,7 @@ def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hy
             smp.set_loglik()
         if predict is not None:
             Yraw = np.asarray(Y, dtype=np.float64)
-            cmean, csd = column_moments(Yraw)
+            cmean, csd = observed_moments(Yraw) if impute else column_moments(Yraw)
             Ystd, obs_in = standardize_rows(predict[0], predict[1], cmean, csd, keep, init.varind)
             smp.set_predict(Ystd, obs_in)
         smp.run(1, N)                                            # dc:90-197
@@ -299,6 +392,11 @@ def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hy
             prd["log_density"] = cl["per_sample"] if cl else np.zeros((0, Ystd.shape[1]))
             prd["lppd"] = cl["lppd"] if cl else np.full(Ystd.shape[1], np.nan)
             prd["count"] = pr["count"]
+        imp = None
+        if impute:
+            Yraw = np.asarray(Y, dtype=np.float64)
+            omean, osd = observed_moments(Yraw)
+            imp = unstandardize_imputation(smp.imputed(), Yraw, omean, osd, keep, init.varind, s0)
     finally:
         smp.close()
     elapsed = time.perf_counter() - t0                           # dc:200 toc
@@ -317,6 +415,8 @@ def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hy
         out += (llk,)
     if predict is not None:
         out += (prd,)
+    if impute:
+        out += (imp,)
     if return_info:
         out += ({"varind": np.asarray(init.varind), "keep": keep, "n": n, "p": p, "P": P,
                  "K": K, "N": N, "seconds": elapsed},)

@@ -106,6 +106,7 @@ class Sampler:
         Y = _f64F(Yd_local)
         if Y.shape != (self.n, self.P, self.g_local):
             raise ValueError(f"Yd_local must be n x P x g_local = {(self.n, self.P, self.g_local)}, got {Y.shape}")
+        self._miss_mask = None                                       # the mask of set_missing goes with the data
         self._check(self.lib.dcfm_set_data(self.h, _ptr(Y)))
 
     def set_data_raw(self, Y, cols):
@@ -121,6 +122,7 @@ class Sampler:
             raise ValueError(f"cols must hold P * g_local = {self.P * self.g_local} indices, got {c.size}")
         sd = np.zeros((self.P, self.g_local), dtype=np.float64, order="F")
         ms = C.c_double(0.0)
+        self._miss_mask = None
         self._check(self.lib.dcfm_set_data_raw(self.h, _ptr(Y), Y.shape[1],
                                                c.ctypes.data_as(C.POINTER(C.c_int64)), _ptr(sd), C.byref(ms)))
         return sd, ms.value
@@ -541,6 +543,56 @@ class Sampler:
         vb = np.maximum(m2 - mean * mean, 0.0)
         return {"mean": mean, "sd_between": np.sqrt(vb), "cvar": cvar, "sd_total": np.sqrt(cvar[:, None] + vb),
                 "maha": maha, "logdet": ld, "count": S}
+
+    # -- missing training data -----------------------------------------------------------
+    def set_missing(self, mask, capacity=None):
+        """Treat entries of the training data as missing (dcfm_set_missing): ``mask`` is (n, P, g_local) in
+        ``Yd_local``'s layout, nonzero = missing.  From the next run on, every iteration ends with a
+        data-augmentation step that redraws the missing entries of the device's Y from
+        ``N(eta_i . lambda_j, 1 / ps_j)`` and refreshes the columns' sums of squares, so the sweep runs on the
+        completed matrix (``get_data()`` reads the current draw).  Call it after ``set_data`` / ``set_data_raw``; a
+        later ``set_data*`` turns it off.  A missing entry whose uploaded value is finite starts there, a NaN one at
+        0.  Up to ``capacity`` saved samples are accumulated for ``imputed()`` (default ``mcmc // thin``; 0 = draw
+        only).  Calling it again replaces the mask and zeroes the accumulators; ``None`` or an all-False mask turns
+        the feature off.  Every rank passes the mask of its own shards.  Not together with ``set_loglik``
+        (DcfmError, DCFM_ERR_UNSUPPORTED, in either order)."""
+        if capacity is None:
+            capacity = int(self.cfg.mcmc) // int(self.cfg.thin)
+        if mask is None:
+            self._check(self.lib.dcfm_set_missing(self.h, None, int(capacity)))
+            self._miss_mask = None
+            return
+        mk = np.asfortranarray(np.asarray(mask) != 0, dtype=np.uint8)
+        if mk.shape != (self.n, self.P, self.g_local):
+            raise ValueError(f"mask must be n x P x g_local = {(self.n, self.P, self.g_local)}, got {mk.shape}")
+        self._check(self.lib.dcfm_set_missing(self.h, mk.ctypes.data_as(C.POINTER(C.c_uint8)), int(capacity)))
+        self._miss_mask = mk.astype(bool) if mk.any() else None
+
+    def imputed_raw(self):
+        """``(mean, m2, nvar, count)`` exactly as dcfm_get_imputed returns them: mean and m2 (n, P, g_local),
+        nvar (P, g_local); all zeros while count is 0."""
+        cnt = C.c_int64(0)
+        mean = np.zeros((self.n, self.P, self.g_local), dtype=np.float64, order="F")
+        m2 = np.zeros((self.n, self.P, self.g_local), dtype=np.float64, order="F")
+        nvar = np.zeros((self.P, self.g_local), dtype=np.float64, order="F")
+        self._check(self.lib.dcfm_get_imputed(self.h, _ptr(mean), _ptr(m2), _ptr(nvar), C.byref(cnt)))
+        return mean, m2, nvar, int(cnt.value)
+
+    def imputed(self) -> dict:
+        """The imputation accumulated so far, in ``Yd_local``'s layout and standardised units: ``mean`` (n, P,
+        g_local) = the posterior mean of ``eta_i . lambda_j`` at a missing entry and the data at an observed one,
+        ``sd_between`` the standard deviation of that conditional mean over the samples, ``sd_total`` =
+        sqrt(avg_s 1 / ps_j + var_between) the total predictive standard deviation (the law of total variance; the
+        between-sample variance m2 - mean^2 clamped at 0), both 0 at observed entries, ``count`` the samples
+        accumulated (the divisor) and ``mask`` the boolean mask in force.  count 0 (and zeros) when nothing is
+        set, the capacity is 0 or nothing was saved yet."""
+        mean, m2, nvar, S = self.imputed_raw()
+        mk = getattr(self, "_miss_mask", None)
+        if mk is None:
+            mk = np.zeros(mean.shape, dtype=bool)
+        vb = np.where(mk, np.maximum(m2 - mean * mean, 0.0), 0.0)
+        tot = np.where(mk, nvar[None, :, :] + vb, 0.0) if S else np.zeros(mean.shape)
+        return {"mean": mean, "sd_between": np.sqrt(vb), "sd_total": np.sqrt(tot), "count": S, "mask": mk}
 
     # -- measurement -----------------------------------------------------------------
     def set_profiling(self, on: bool):

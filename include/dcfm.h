@@ -494,6 +494,55 @@ int  dcfm_set_predict(dcfm_handle *h, const double *Ynew, const uint8_t *observe
 int  dcfm_get_predict(dcfm_handle *h, double *mean, double *m2, double *cvar, double *maha, double *logdet,
                       int64_t *count);
 
+/* ---- missing training data: an on-device imputation step ------------------------------------------------------
+ * Given eta, Lambda and ps every missing entry of the training matrix is conditionally independent,
+ * Y_ij | . ~ N(eta_i . lambda_j, 1 / ps_j), so one data-augmentation step per Gibbs iteration is a valid extension
+ * of the sweep: behind the loading rows of iteration t (X, Z, Lambda, ps of t final, before the sample is saved)
+ * the device redraws the missing entries in place in Y and rewrites yy_j = sum_i Y_ij^2 of their columns; every
+ * other kernel keeps reading Y as it does without a mask.  For a missing (i, j) of local shard m (global shard mg)
+ *   mu = sum_{k < K} eta_ik lambda_jk (k ascending),  eta_ik = sqrt(rho) X_ik + sqrt(1 - rho) Z_mik,
+ *   Y_ij = mu + z / sqrt(ps_j),
+ * z the standard normal at the Philox counter (site 13, shard mg, row j, normal index i, iteration): the value
+ * dcfm_rng_fill_rows(device, cfg.seed, 0, 0, 13, mg, iteration, P, n, P n, out) returns at out[j n + i].  With
+ * DCFM_FLAG_INJECT_DRAWS these normals still come from Philox at cfg.seed: dcfm_draws_view keeps its layout and has
+ * no member for them.  yy_j is rewritten as yy_obs_j + sum_{i missing} Y_ij^2 in a fixed order, never as an
+ * increment of its old value.  The Rao-Blackwellised by-products are, per missing entry, the posterior mean of mu
+ * and, by the law of total variance, Var[Y_ij | observed] = nvar_j + m2_ij - mean_ij^2 (csrc/impute.hip has the
+ * kernels).
+ *
+ * dcfm_set_missing: mask_local is n x P x g_local bytes, column-major, the layout of dcfm_set_data's Yd_local;
+ * nonzero = missing.  After dcfm_set_data / dcfm_set_data_raw only (else DCFM_ERR_INVALID, "set_data first"); a
+ * later dcfm_set_data* turns the feature off, because the mask belongs to the data.  A NULL or all-zero mask turns
+ * it off and frees its buffers (yy of the mask's columns then is what dcfm_set_data would form from the completed
+ * matrix); nothing is allocated or launched until a call with a missing entry.  Not collective: every rank passes the
+ * mask of its own shards, nothing of Y crosses ranks, any number of ranks.  Start values: a missing entry whose
+ * current device value is finite keeps it (a completed matrix from dcfm_get_data continues a chain), a non-finite
+ * one (the caller passed NaN) becomes 0, the standardised column mean.  yy_obs_j, the sum of squares of column j's
+ * observed entries, is formed once here by a direct sum in row order.  `capacity` is the number of saved samples
+ * accumulated for dcfm_get_imputed: 0 = draw and rewrite only, no accumulators; later saved samples are ignored;
+ * a second call replaces the mask and zeroes the accumulators and the count.  The step runs at every iteration, in
+ * both launch schedules and at every K, on the sweep stream, booked under DCFM_K_SAVE.  No floating-point atomics,
+ * one sample added per launch in sample order: the same inputs give the same bits, in one dcfm_run call or one
+ * iteration per call.
+ * Together with dcfm_set_loglik it is DCFM_ERR_UNSUPPORTED, in either call order, and the earlier setting stays:
+ * that read-out would be the likelihood of the completed data, not of the observed entries.  More than 2^31 - 1
+ * missing entries on a rank: DCFM_ERR_UNSUPPORTED.  A failed call leaves the previous setting as it was.
+ * Device bytes: 20 per missing entry + 16 with capacity > 0, and 16 (+ 8) per column with a missing entry.
+ * After DCFM_ERR_NUMERIC the imputed entries of Y may be non-finite: dcfm_set_state / dcfm_init_state clear the
+ * handle's error as before, and the caller must repeat dcfm_set_data and dcfm_set_missing.  dcfm_get_data returns
+ * the completed matrix with the current draw; reading it every few saved samples is multiple imputation.
+ * Errors (DCFM_ERR_INVALID): NULL handle ("null handle"), capacity < 0, no data.
+ *
+ * dcfm_get_imputed: count (required) receives the number of samples accumulated; the other outputs are nullable.
+ * mean and m2 are n x P x g_local column-major: at a missing position sum mu / count and sum mu^2 / count (count
+ * is the number actually accumulated, the population form), at an observed one Y_ij and Y_ij^2; nvar is P x
+ * g_local: sum (1 / ps_j) / count for a column with a missing entry, 0 elsewhere.  Blocks (synchronises the sweep
+ * stream), does not disturb a later dcfm_run, not collective.  With nothing set, capacity == 0 or no sample yet:
+ * *count = 0, DCFM_OK and the other outputs are not written.  After DCFM_ERR_NUMERIC it returns what the device
+ * holds.  Errors (DCFM_ERR_INVALID): NULL handle ("null handle"), NULL count ("null argument"). */
+int  dcfm_set_missing(dcfm_handle *h, const uint8_t *mask_local, int64_t capacity);
+int  dcfm_get_imputed(dcfm_handle *h, double *mean, double *m2, double *nvar, int64_t *count);
+
 /* ---- measurement --------------------------------------------------------- */
 /* Per-kernel HIP-event timing on the handle's stream (off by default).
  * Kernel ids: DCFM_K_* below.  Times are accumulated device milliseconds. */

@@ -61,6 +61,15 @@
  *                                         average conditional variance; total variance cvar + m2 - mean.^2), maha
  *                                         nt x S = y_A' * inv(Sigma_AA_s) * y_A and logdet S x 1 (empty with
  *                                         nothing set)
+ *   dcfm_mex('set_missing', h, mask[, capacity])   treat entries of the data as missing: mask n x P x g double in
+ *                                         Yd's layout, nonzero = missing ([] turns it off); after 'set_data' only;
+ *                                         every later iteration redraws them on the device; capacity saved samples
+ *                                         are accumulated (default mcmc / thin; 0: draw only); not with 'set_loglik'
+ *   [mean, m2, nvar, count] = dcfm_mex('imputed', h)   the accumulated imputation: mean and m2 n x P x g (at a missing
+ *                                         entry the averages of eta_i . lambda_j and of its square, at an observed one
+ *                                         Yd and Yd.^2), nvar P x g the average 1 / ps_j of the columns with a missing
+ *                                         entry (total variance nvar + m2 - mean.^2), count the samples accumulated
+ *                                         (count 0: empty arrays)
  *   e = dcfm_mex('error', h, U, s, iters)[||S-S0||_F, ||S0||_F, ||S-S0||_2] vs S0 = UU' + diag(s)
  *   dcfm_mex('set_trace', h, cap); T = dcfm_mex('get_trace', h)     chain trace (count x 4)
  *   dcfm_mex('destroy', h)
@@ -527,6 +536,47 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
             ck(t->h, dcfm_get_predict(t->h, nt > 0 ? mxGetDoubles(o[0]) : NULL, nt > 0 ? mxGetDoubles(o[1]) : NULL,
                                       mxGetDoubles(o[2]), nt > 0 ? mxGetDoubles(o[3]) : NULL, mxGetDoubles(o[4]), &cnt));
         for (int i = 0; i < 5; ++i)
+            if (i == 0 || i < nlhs) plhs[i] = o[i];
+            else mxDestroyArray(o[i]);
+    } else if (!strcmp(cmd, "set_missing")) {        /* dcfm_mex('set_missing', h, mask[, capacity]) */
+        if (nrhs != 3 && nrhs != 4)
+            mexErrMsgIdAndTxt("dcfm:nargs", "'%s' takes 2 or 3 arguments, got %d", cmd, nrhs - 1);
+        /* the argument that needs no handle first: a malformed call never reaches the library */
+        const double cap = nrhs > 3 ? scalar(prhs[3], "capacity") : -1;
+        if (nrhs > 3 && (cap < 0 || cap > 9007199254740992.0 || cap != (double)(int64_t)cap))
+            mexErrMsgIdAndTxt("dcfm:arg", "capacity must be a non-negative integer");
+        slot *t = get(prhs[1]);
+        const int64_t numel = t->n * t->P * t->g;    /* the bytes the library reads */
+        const int64_t capacity = nrhs > 3 ? (int64_t)cap : (t->thin > 0 ? t->mcmc / t->thin : 0);
+        const mxArray *mk = prhs[2];
+        if (!mxIsDouble(mk) || mxIsComplex(mk) ||
+            (mxGetNumberOfElements(mk) != 0 && (int64_t)mxGetNumberOfElements(mk) != numel))
+            mexErrMsgIdAndTxt("dcfm:arg", "mask must be a real double n x P x g array of %lld elements, or empty",
+                              (long long)numel);
+        if (mxGetNumberOfElements(mk) == 0) {        /* []: off */
+            ck(t->h, dcfm_set_missing(t->h, NULL, capacity));
+        } else {
+            uint8_t *mask = (uint8_t *)mxMalloc((mwSize)numel);
+            const double *md = mxGetDoubles(mk);
+            for (int64_t q = 0; q < numel; ++q) mask[q] = md[q] != 0.0;
+            const int rc = dcfm_set_missing(t->h, mask, capacity);
+            mxFree(mask);
+            ck(t->h, rc);
+        }
+    } else if (!strcmp(cmd, "imputed")) {            /* [mean, m2, nvar, count] = dcfm_mex('imputed', h) */
+        nargs(nrhs, 2, cmd);
+        slot *t = get(prhs[1]);
+        int64_t cnt = 0;
+        ck(t->h, dcfm_get_imputed(t->h, NULL, NULL, NULL, &cnt));
+        const mwSize on = cnt > 0 ? 1 : 0;           /* the library writes nothing while the count is 0 */
+        const mwSize d3[3] = {on * (mwSize)t->n, on * (mwSize)t->P, on * (mwSize)t->g};
+        mxArray *o[4];                               /* the sizes the library writes */
+        o[0] = mxCreateNumericArray(3, d3, mxDOUBLE_CLASS, mxREAL);
+        o[1] = mxCreateNumericArray(3, d3, mxDOUBLE_CLASS, mxREAL);
+        o[2] = mxCreateDoubleMatrix(on * (mwSize)t->P, on * (mwSize)t->g, mxREAL);
+        o[3] = mxCreateDoubleScalar((double)cnt);
+        if (cnt > 0) ck(t->h, dcfm_get_imputed(t->h, mxGetDoubles(o[0]), mxGetDoubles(o[1]), mxGetDoubles(o[2]), &cnt));
+        for (int i = 0; i < 4; ++i)
             if (i == 0 || i < nlhs) plhs[i] = o[i];
             else mxDestroyArray(o[i]);
     } else if (!strcmp(cmd, "destroy")) {

@@ -212,10 +212,12 @@ __global__ __launch_bounds__(256, 2) void k_assemble(Dims d, const double *__res
 // WHICH (DCFM_SIGMA_*): the mean S, the second moment S2, or the posterior standard deviation
 // sqrt(max(0, rs S2 - (rs S)^2)) formed here from both (rs = effsamp / saved samples), so
 // neither matrix leaves the device to be combined.
+// dset: the diagonal is not read but set to dval (the partial correlations: R(s)_aa = 1 for every sample, so
+// both moments are saved / effsamp and the standard deviation 0 by definition, not by a rounded sum)
 template <int WHICH>
 __global__ __launch_bounds__(256) void k_sigma_pack(const double *__restrict__ S, const double *__restrict__ S2,
                                                     double rs, int p, int T0, int T1, int c0, int nc,
-                                                    double *__restrict__ out) {
+                                                    double *__restrict__ out, int dset, double dval) {
     auto at = [&](size_t o) {
         if (WHICH == 0) return S[o];
         if (WHICH == 1) return S2[o];
@@ -231,7 +233,7 @@ __global__ __launch_bounds__(256) void k_sigma_pack(const double *__restrict__ S
     if (need_lo) {
         for (int yy = ty; yy < 32; yy += 8) {      // rows r = r0 + yy, columns c = cb + tx
             const int r = r0 + yy, c = cb + tx;
-            lo[yy][tx] = (r >= R0 && r < R1 && c < c0 + nc && r >= c) ? at(sig_off(r, c, T0)) : 0.0;
+            lo[yy][tx] = (r >= R0 && r < R1 && c < c0 + nc && r >= c) ? ((dset && r == c) ? dval : at(sig_off(r, c, T0))) : 0.0;
         }
     }
     __syncthreads();
@@ -280,13 +282,17 @@ void launch_assemble(const Dims &d, const Bufs &b, const double *Lb, const doubl
                        b.tiles, b.T0, b.Sigma);
 }
 void launch_sigma_pack(const double *S, const double *S2, int which, double rs, int p, int T0, int T1, int c0,
-                       int nc, double *out, hipStream_t s) {
+                       int nc, double *out, hipStream_t s, const double *diag) {
     const int R1 = std::min(p, T1 * ASM_TILE);
     if (nc <= 0 || R1 <= 0 || T1 <= T0) return;
     const dim3 grid(cdiv(R1, 32), cdiv(nc, 32));
-    if (which == 0) hipLaunchKernelGGL(k_sigma_pack<0>, grid, dim3(256), 0, s, S, S2, rs, p, T0, T1, c0, nc, out);
-    else if (which == 1) hipLaunchKernelGGL(k_sigma_pack<1>, grid, dim3(256), 0, s, S, S2, rs, p, T0, T1, c0, nc, out);
-    else hipLaunchKernelGGL(k_sigma_pack<2>, grid, dim3(256), 0, s, S, S2, rs, p, T0, T1, c0, nc, out);
+    const int dset = diag ? 1 : 0;
+    const double dval = diag ? *diag : 0.0;
+    if (which == 0)
+        hipLaunchKernelGGL(k_sigma_pack<0>, grid, dim3(256), 0, s, S, S2, rs, p, T0, T1, c0, nc, out, dset, dval);
+    else if (which == 1)
+        hipLaunchKernelGGL(k_sigma_pack<1>, grid, dim3(256), 0, s, S, S2, rs, p, T0, T1, c0, nc, out, dset, dval);
+    else hipLaunchKernelGGL(k_sigma_pack<2>, grid, dim3(256), 0, s, S, S2, rs, p, T0, T1, c0, nc, out, dset, dval);
 }
 void launch_sigma_unpack(const double *recv, int p, int c0, int nc, const int *Tb, const long long *base,
                          int nranks, double *out, hipStream_t s) {

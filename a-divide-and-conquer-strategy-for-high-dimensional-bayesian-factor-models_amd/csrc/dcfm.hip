@@ -243,15 +243,20 @@ static int alloc_buffers(dcfm_handle *h) {
     if (c.flags & DCFM_FLAG_SIGMA_M2) {   // second moment beside the mean, and each saved sample's own omega
         TRY(dalloc(h, &b.Sigma2, (size_t)(tri(b.T1) - tri(b.T0)) * ASM_TILE * ASM_TILE));
     }
-    if (c.flags & DCFM_FLAG_PRECISION_MEAN) {   // mean of the per-sample inverse, its factor panels and K x K scratch
+    if (c.flags & DCFM_FLAG_PRECISION_MEAN)     // mean of the per-sample inverse
+        TRY(dalloc(h, &h->pm.Prec, (size_t)(tri(b.T1) - tri(b.T0)) * ASM_TILE * ASM_TILE));
+    if (c.flags & DCFM_FLAG_PARTIAL_CORR) {     // mean and second moment of the per-sample partial correlations
+        TRY(dalloc(h, &h->pc.PC, (size_t)(tri(b.T1) - tri(b.T0)) * ASM_TILE * ASM_TILE));
+        TRY(dalloc(h, &h->pc.PC2, (size_t)(tri(b.T1) - tri(b.T0)) * ASM_TILE * ASM_TILE));
+    }
+    if (c.flags & (DCFM_FLAG_PRECISION_MEAN | DCFM_FLAG_PARTIAL_CORR)) {   // their factor panels and K x K scratch
         PrecMean &pm = h->pm;
-        TRY(dalloc(h, &pm.Prec, (size_t)(tri(b.T1) - tri(b.T0)) * ASM_TILE * ASM_TILE));
         pm.KH = round_up(h->B * d.K, ASM_KC);
         TRY(dalloc(h, &pm.pfac, p * 4 * (size_t)pm.KH));
         TRY(dalloc(h, &pm.pscr, precision_mean_scratch_doubles(d.g, d.K, h->B)));
         HIPC(h, precision_mean_setup());
     }
-    if (c.flags & (DCFM_FLAG_SIGMA_M2 | DCFM_FLAG_PRECISION_MEAN)) {   // each saved sample's own omega
+    if (c.flags & (DCFM_FLAG_SIGMA_M2 | DCFM_FLAG_PRECISION_MEAN | DCFM_FLAG_PARTIAL_CORR)) {   // each saved sample's own omega
         TRY(dalloc(h, &b.wslot[0], p * (size_t)h->B));
         TRY(dalloc(h, &b.wslot[1], p * (size_t)h->B));
     }
@@ -410,8 +415,12 @@ static int flush_batch(dcfm_handle *h) {
         launch_assemble(d, b, b.Lb[lb], b.wsum[lb], kext, 1.0 / effsamp, h->sasm);
         // DCFM_FLAG_SIGMA_M2: the batch's samples one by one into the second moment
         if (b.Sigma2) launch_assemble_m2(d, b, b.Lb[lb], b.wslot[lb], h->batch, h->B, 1.0 / effsamp, h->sasm);
-        // DCFM_FLAG_PRECISION_MEAN: the batch's per-sample inverses into the precision mean
-        if (h->pm.Prec) launch_precision_mean(d, b, h->pm, b.Lb[lb], b.wslot[lb], h->batch, h->B, 1.0 / effsamp, h->sasm);
+        // the factor panels of the batch's per-sample inverses, once for both of their readers
+        if (h->pm.pfac) launch_precision_panels(d, b, h->pm, b.Lb[lb], b.wslot[lb], h->batch, h->B, h->sasm);
+        // DCFM_FLAG_PRECISION_MEAN: the inverses into the precision mean
+        if (h->pm.Prec) launch_precision_mean(d, b, h->pm, b.wslot[lb], h->batch, h->B, 1.0 / effsamp, h->sasm);
+        // DCFM_FLAG_PARTIAL_CORR: the panels scaled in place, the partial correlations into their two moments
+        if (h->pc.PC) launch_partial_corr(d, b, h->pm, h->pc, b.wslot[lb], h->batch, h->B, 1.0 / effsamp, h->sasm);
     }
     HIPC(h, hipGetLastError());
     HIPC(h, hipMemsetAsync(b.wsum[lb], 0, (size_t)d.p * sizeof(double), h->sasm));   // k_save adds into it

@@ -23,10 +23,12 @@
 //   sloc   [G][KW], sall [g][KW]  column sums (all-gathered)
 //   Lb     [2][p][LDB]   saved Lambda rows of an assembly batch (double-buffered), sample s at cols s*K..
 //   wsum   [2][p]        sum of saved omega of the batch
-//   wslot  [2][p][B]     DCFM_FLAG_SIGMA_M2 / _PRECISION_MEAN: each saved sample's own omega (slot s of row a at a*B + s)
+//   wslot  [2][p][B]     DCFM_FLAG_SIGMA_M2 / _PRECISION_MEAN / _PARTIAL_CORR: each saved sample's own omega (slot s of row a at a*B + s)
 //   Prec   [ntiles][128][128]  DCFM_FLAG_PRECISION_MEAN: mean of the per-sample Sigma^{-1}, laid out as Sigma
-//   pfac   [p][4 KH]     DCFM_FLAG_PRECISION_MEAN: the factor panels of a flush (precision_mean.hip), KH = round_up(B K, 16);
+//   pfac   [p][4 KH]     DCFM_FLAG_PRECISION_MEAN / _PARTIAL_CORR: the factor panels of a flush (precision_mean.hip), KH = round_up(B K, 16);
 //                        pscr [(2 g + 1) B][K][K] the shards' H_m, B_m^{-1} and the slots' S^{-1}
+//   PC, PC2 [ntiles][128][128]  DCFM_FLAG_PARTIAL_CORR: mean and second moment of the per-sample partial
+//                        correlations, laid out as Sigma (partial_corr.hip; it shares pfac, pscr, wslot)
 //   Sigma2 [ntiles][128][128]  DCFM_FLAG_SIGMA_M2: second moment of the per-sample Sigma, laid out as Sigma
 //   Sigma  [ntiles][128][128]  this rank's block of the lower triangle of Sigmaout, tile-packed:
 //                        rank r owns the contiguous tile rows [T0, T1) (balanced by tile count,
@@ -230,10 +232,16 @@ struct Impute {
 };
 // Precision mean (precision_mean.hip, DCFM_FLAG_PRECISION_MEAN; all null when off).  Kept out of Bufs, which
 // the sweep's kernels take by value: Prec the accumulator (laid out as Bufs::Sigma), pfac the factor panels of
-// a flush, pscr the K x K scratch, KH the columns of a quarter of pfac (B K rounded up to ASM_KC)
+// a flush, pscr the K x K scratch, KH the columns of a quarter of pfac (B K rounded up to ASM_KC).
+// DCFM_FLAG_PARTIAL_CORR alone allocates pfac and pscr (the panel stage is shared) and leaves Prec null
 struct PrecMean {
     double *Prec, *pfac, *pscr;
     int KH;
+};
+// Partial correlations (partial_corr.hip, DCFM_FLAG_PARTIAL_CORR; null when off): PC the mean and PC2 the second
+// moment of the per-sample R(s), both laid out as Bufs::Sigma
+struct PartialCorr {
+    double *PC, *PC2;
 };
 // Bufs::sync: [0] the X operators (k_xdraw, several ranks), [1] spare, [2, 2 + 256) chunk counters of the A sum, [SYNC_ZM, SYNC_ZM + G) the
 // per-shard Z-operator counters (the fused W pass draws Z once its shard's operators are out)
@@ -330,16 +338,29 @@ void launch_assemble(const Dims &d, const Bufs &b, const double *Lb, const doubl
 void launch_assemble_m2(const Dims &d, const Bufs &b, const double *Lb, const double *wslot, int nslots, int B,
                         double inv_eff, hipStream_t s);
 // precision_mean.hip: pm.Prec += (1 / effsamp) sum over the batch's nslots samples of Sigma(s)^{-1}, from the
-// gathered Lb slots and wslot [p][B] of ALL g shards; setup once per process before the first launch
+// gathered Lb slots and wslot [p][B] of ALL g shards; setup once per process before the first launch.
+// launch_precision_panels: the panel stage (k_pm_shard, k_pm_s, k_pm_panels) into pm.pfac, once per flush for the
+// precision mean and the partial correlations; launch_precision_mean: the two accumulation passes behind it
 size_t precision_mean_scratch_doubles(int g, int K, int B);
 hipError_t precision_mean_setup();
-void launch_precision_mean(const Dims &d, const Bufs &b, const PrecMean &pm, const double *Lb, const double *wslot, int nslots, int B,
+void launch_precision_panels(const Dims &d, const Bufs &b, const PrecMean &pm, const double *Lb, const double *wslot,
+                             int nslots, int B, hipStream_t s);
+void launch_precision_mean(const Dims &d, const Bufs &b, const PrecMean &pm, const double *wslot, int nslots, int B,
                            double inv_eff, hipStream_t s);
+// the same tile loop over panels scaled per row by k_pc_scale: PC += (1 / effsamp) sum_s R(s), the off-diagonal
+// sign +, the diagonal exactly nslots / effsamp (G pass, then A pass)
+void launch_pc_mean(const Dims &d, const Bufs &b, const PrecMean &pm, int nslots, double inv_eff, double *PC,
+                    hipStream_t s);
+// partial_corr.hip, behind launch_precision_mean on the same stream: scales pm.pfac in place (k_pc_scale), then
+// pc.PC += (1 / effsamp) sum_s R(s) and pc.PC2 += (1 / effsamp) sum_s R(s).^2 over the batch's nslots samples
+void launch_partial_corr(const Dims &d, const Bufs &b, const PrecMean &pm, const PartialCorr &pc, const double *wslot,
+                         int nslots, int B, double inv_eff, hipStream_t s);
 // column stripe [c0, c0 + nc) of Sigmaout from a rank's tile-packed block (tile rows [T0, T1)):
 // the rank's packed windows (win_lo / win_off; with one rank = the dense p x nc stripe).
-// which (DCFM_SIGMA_*): 0 the mean S, 1 the second moment S2, 2 sqrt(max(0, rs S2 - (rs S)^2))
+// which (DCFM_SIGMA_*): 0 the mean S, 1 the second moment S2, 2 sqrt(max(0, rs S2 - (rs S)^2)).
+// diag (host pointer, nullable): the value written on the diagonal instead of the one read
 void launch_sigma_pack(const double *S, const double *S2, int which, double rs, int p, int T0, int T1, int c0,
-                       int nc, double *out, hipStream_t s);
+                       int nc, double *out, hipStream_t s, const double *diag = nullptr);
 // root of the gather: the dense p x nc stripe from every rank's packed windows, rank k's at
 // recv + base[k]; Tb[0..nranks] are the ranks' tile-row boundaries (device arrays)
 void launch_sigma_unpack(const double *recv, int p, int c0, int nc, const int *Tb, const long long *base,

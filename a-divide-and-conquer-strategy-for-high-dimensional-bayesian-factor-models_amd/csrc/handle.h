@@ -95,6 +95,8 @@ struct dcfm_handle {
     int64_t imp_cap = 0, imp_n = 0;
     // posterior mean of the precision matrix (DCFM_FLAG_PRECISION_MEAN, precision_mean.hip): null when off
     PrecMean pm{};
+    // posterior mean and second moment of the partial correlations (DCFM_FLAG_PARTIAL_CORR, partial_corr.hip)
+    PartialCorr pc{};
     bool prof = false;
     uint32_t prof_mask = 0;       // kernel ids (bit DCFM_K_*) timed with events
     int prof_stride = 1;          // time one in prof_stride launches of each (dcfm_set_profiling_stride)

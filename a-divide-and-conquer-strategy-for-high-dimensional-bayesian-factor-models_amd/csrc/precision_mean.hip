@@ -16,7 +16,9 @@
 //
 // Every rank forms the panels of ALL g shards from the gathered Lb / wslot of the flush (p K^2 per sample
 // against p^2 K for the accumulation), so the sum over the shards needs no collective and every rank feeds
-// the same factor bytes to the tiles it owns.  Four launches per flush, in stream order (no hand-off
+// the same factor bytes to the tiles it owns.  The panel stage (launch_precision_panels: the first three kernels)
+// runs once per flush for this file's accumulation and for partial_corr.hip, which scales the panels in place
+// behind launch_precision_mean.  Four launches per flush, in stream order (no hand-off
 // between blocks, no floating-point atomics, no data-dependent trip count: a NaN state runs through):
 //   k_pm_shard   (shard, slot): G_m by v_mfma_f64_16x16x4 over the shard's rows (staged 32 at a time, weighted
 //                by 1 / omega), B_m^{-1} in LDS (gj_invert), H_m = B_m^{-1} G_m;
@@ -193,9 +195,11 @@ __global__ __launch_bounds__(256) void k_pm_panels(const double *__restrict__ Lb
     });
 }
 
-// k_assemble's tile loop with a left (rows) and a right (columns) panel of Fb.  APASS: the A half
+// k_assemble's tile loop with a left (rows) and a right (columns) panel of Fb.  APASS: the A half.
+// PC (partial_corr.hip): the panels are scaled by 1 / sqrt(d_a(s)), the sum is the per-sample partial
+// correlation: sign +, and the diagonal entry is the count nslots / effsamp itself (G pass; the A pass adds 0)
 constexpr int PKC = ASM_KC, PLD = ASM_TILE + 16;
-template <bool APASS>
+template <bool APASS, bool PC = false>
 __global__ __launch_bounds__(256, 2) void k_assemble_prec(Dims d, const double *__restrict__ Fb, int LDF, int offL,
                                                           int offR, int kext, const double *__restrict__ wslot,
                                                           int B, int nslots, double inv_eff,
@@ -283,9 +287,10 @@ __global__ __launch_bounds__(256, 2) void k_assemble_prec(Dims d, const double *
             for (int v = 0; v < 4; ++v) {
                 const int b = b0 + 16 * v + r;
                 if (a < p && b <= a) {
-                    double val = -inv_eff * acc[u][v][g];
+                    double val = (PC ? inv_eff : -inv_eff) * acc[u][v][g];
                     if (APASS && sb[v] != sa) val = 0.0;
-                    if (!APASS && a == b) {     // sum_s 1 / omega_a(s), the batch's slots in slot order
+                    if (PC && a == b) val = APASS ? 0.0 : (double)nslots * inv_eff;
+                    if (!PC && !APASS && a == b) {     // sum_s 1 / omega_a(s), the batch's slots in slot order
                         double ps = 0.0;
                         for (int s = 0; s < nslots; ++s) ps += 1.0 / wslot[(size_t)a * B + s];
                         val = fma(ps, inv_eff, val);
@@ -313,10 +318,10 @@ hipError_t precision_mean_setup() {
     return e;
 }
 
-void launch_precision_mean(const Dims &d, const Bufs &b, const PrecMean &pm, const double *Lb, const double *wslot, int nslots, int B,
-                           double inv_eff, hipStream_t s) {
+void launch_precision_panels(const Dims &d, const Bufs &b, const PrecMean &pm, const double *Lb, const double *wslot,
+                             int nslots, int B, hipStream_t s) {
     if (nslots == 0) return;
-    const int K = d.K, g = d.g, KH = pm.KH, LDF = 4 * KH;
+    const int K = d.K, g = d.g, KH = pm.KH;
     double *scr = pm.pscr, *Sinv = scr + (size_t)2 * g * B * K * K;
     hipLaunchKernelGGL(k_pm_shard, dim3(g, nslots), dim3(256), pm_shard_doubles(K) * sizeof(double), s, Lb, b.LDB,
                        wslot, B, d.P, K, g, d.rho, scr);
@@ -324,12 +329,27 @@ void launch_precision_mean(const Dims &d, const Bufs &b, const PrecMean &pm, con
     hipLaunchKernelGGL(k_pm_panels, dim3(cdiv(d.P, PM_PROWS), g, nslots), dim3(256),
                        pm_panel_doubles(K) * sizeof(double), s, Lb, b.LDB, wslot, B, d.P, K, g, d.rho, scr, Sinv,
                        nslots, KH, pm.pfac);
-    if (b.ntiles == 0) return;
+}
+
+void launch_precision_mean(const Dims &d, const Bufs &b, const PrecMean &pm, const double *wslot, int nslots, int B,
+                           double inv_eff, hipStream_t s) {
+    if (nslots == 0 || b.ntiles == 0) return;
+    const int K = d.K, KH = pm.KH, LDF = 4 * KH;
     const int kext = (nslots * K + 3) & ~3;
     hipLaunchKernelGGL(k_assemble_prec<false>, dim3(b.ntiles), dim3(256), 0, s, d, pm.pfac, LDF, 0, 2 * KH, kext,
                        wslot, B, nslots, inv_eff, b.tiles, b.T0, pm.Prec);
     hipLaunchKernelGGL(k_assemble_prec<true>, dim3(b.ntiles), dim3(256), 0, s, d, pm.pfac, LDF, KH, 3 * KH, kext,
                        wslot, B, nslots, inv_eff, b.tiles, b.T0, pm.Prec);
+}
+
+void launch_pc_mean(const Dims &d, const Bufs &b, const PrecMean &pm, int nslots, double inv_eff, double *PC,
+                    hipStream_t s) {
+    if (nslots == 0 || b.ntiles == 0) return;
+    const int KH = pm.KH, LDF = 4 * KH, kext = (nslots * d.K + 3) & ~3;
+    hipLaunchKernelGGL((k_assemble_prec<false, true>), dim3(b.ntiles), dim3(256), 0, s, d, pm.pfac, LDF, 0, 2 * KH, kext,
+                       nullptr, 0, nslots, inv_eff, b.tiles, b.T0, PC);
+    hipLaunchKernelGGL((k_assemble_prec<true, true>), dim3(b.ntiles), dim3(256), 0, s, d, pm.pfac, LDF, KH, 3 * KH, kext,
+                       nullptr, 0, nslots, inv_eff, b.tiles, b.T0, PC);
 }
 
 }  // namespace dcfm

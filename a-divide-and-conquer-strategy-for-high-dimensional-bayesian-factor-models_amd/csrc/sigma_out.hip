@@ -5,8 +5,12 @@
 // Columns [col0, col0 + ncols) of one posterior moment of Sigma (DCFM_SIGMA_*), gathered to the
 // root rank: the one body of dcfm_get_sigma_cols (the mean) and dcfm_get_sigma_moment_cols.  The
 // moments differ only in what k_sigma_pack reads from the rank's block(s).
-// prec: the same read-out pointed at the precision mean (dcfm_get_precision_mean_cols; which = DCFM_SIGMA_MEAN).
-static int sigma_moment_cols(dcfm_handle *h, int which, int64_t col0, int64_t ncols, double *out, bool prec = false) {
+// src: the same read-out pointed at the precision mean (SRC_PREC: dcfm_get_precision_mean_cols; which =
+// DCFM_SIGMA_MEAN) or at the two moments of the partial correlations (SRC_PCORR: dcfm_get_partial_corr_cols).
+enum MomentSrc { SRC_SIGMA = 0, SRC_PREC, SRC_PCORR };
+static const char *const PCORR_FLAG_MSG = "the partial correlations need DCFM_FLAG_PARTIAL_CORR at dcfm_create";
+static int sigma_moment_cols(dcfm_handle *h, int which, int64_t col0, int64_t ncols, double *out, MomentSrc src = SRC_SIGMA) {
+    const bool prec = src == SRC_PREC, pcorr = src == SRC_PCORR;
     if (!h) return fail(h, DCFM_ERR_INVALID, "null handle");
     Dims &d = h->d;
     const int root = 0;
@@ -16,11 +20,13 @@ static int sigma_moment_cols(dcfm_handle *h, int which, int64_t col0, int64_t nc
         code = fail(h, DCFM_ERR_INVALID, "sigma moment %d: DCFM_SIGMA_MEAN, _M2 or _SD", which);
     else if (prec && !h->pm.Prec)
         code = fail(h, DCFM_ERR_INVALID, "the precision mean needs DCFM_FLAG_PRECISION_MEAN at dcfm_create");
-    else if (which != DCFM_SIGMA_MEAN && !h->b.Sigma2)
+    else if (pcorr && !h->pc.PC) code = fail(h, DCFM_ERR_INVALID, "%s", PCORR_FLAG_MSG);
+    else if (!pcorr && which != DCFM_SIGMA_MEAN && !h->b.Sigma2)
         code = fail(h, DCFM_ERR_INVALID, "the second moment and the standard deviation of Sigma need "
                                          "DCFM_FLAG_SIGMA_M2 at dcfm_create");
     else if (which == DCFM_SIGMA_SD && h->saved < 1)
-        code = fail(h, DCFM_ERR_INVALID, "standard deviation of Sigma: no saved sample yet");
+        code = fail(h, DCFM_ERR_INVALID, "standard deviation of %s: no saved sample yet",
+                    pcorr ? "the partial correlations" : "Sigma");
     else if (!out && d.rank == root) code = fail(h, DCFM_ERR_INVALID, "null output on the root rank");
     else if (col0 < 0 || ncols < 0 || col0 + ncols > d.p)
         code = fail(h, DCFM_ERR_INVALID, "columns [%lld, %lld) outside 0..p = %d", (long long)col0,
@@ -69,8 +75,10 @@ static int sigma_moment_cols(dcfm_handle *h, int which, int64_t col0, int64_t nc
     double *buf = static_cast<double *>(q);
     double *mine = is_root ? buf + base[d.rank] : buf;
     int rc = DCFM_OK;
-    launch_sigma_pack(prec ? h->pm.Prec : h->b.Sigma, h->b.Sigma2, which, rs, d.p, h->b.T0, h->b.T1, (int)col0, (int)ncols, mine,
-                      h->stream);
+    // R(s)_aa = 1 for every saved sample: the diagonal of both moments is the scaled count itself, its SD 0
+    const double pdiag = which == DCFM_SIGMA_SD ? 0.0 : (double)h->saved / ((double)h->cfg.mcmc / (double)h->cfg.thin);
+    launch_sigma_pack(pcorr ? h->pc.PC : (prec ? h->pm.Prec : h->b.Sigma), pcorr ? h->pc.PC2 : h->b.Sigma2, which, rs, d.p,
+                      h->b.T0, h->b.T1, (int)col0, (int)ncols, mine, h->stream, pcorr ? &pdiag : nullptr);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) rc = fail(h, DCFM_ERR_HIP, "sigma_pack: %s", hipGetErrorString(e));
     double *dense = buf;   // one rank: its windows are the dense stripe
@@ -109,15 +117,16 @@ static int sigma_moment_cols(dcfm_handle *h, int which, int64_t col0, int64_t nc
 }
 
 // the whole p x p moment in column stripes of <= 2 GiB
-static int sigma_moment(dcfm_handle *h, int which, double *out, bool prec = false) {
+static int sigma_moment(dcfm_handle *h, int which, double *out, MomentSrc src = SRC_SIGMA) {
     if (!h) return fail(h, DCFM_ERR_INVALID, "null handle");
-    if (prec && !h->pm.Prec)
+    if (src == SRC_PREC && !h->pm.Prec)
         return fail(h, DCFM_ERR_INVALID, "the precision mean needs DCFM_FLAG_PRECISION_MEAN at dcfm_create");
+    if (src == SRC_PCORR && !h->pc.PC) return fail(h, DCFM_ERR_INVALID, "%s", PCORR_FLAG_MSG);
     if (!out && h->d.rank == 0) return fail(h, DCFM_ERR_INVALID, "null output on the root rank");
     const int64_t p = h->d.p;
     const int64_t chunk = std::max<int64_t>(32, std::min<int64_t>(p, ((int64_t)1 << 28) / p));
     for (int64_t c = 0; c < p; c += chunk) {
-        const int rc = sigma_moment_cols(h, which, c, std::min(chunk, p - c), out ? out + (size_t)c * p : nullptr, prec);
+        const int rc = sigma_moment_cols(h, which, c, std::min(chunk, p - c), out ? out + (size_t)c * p : nullptr, src);
         if (rc) return rc;
     }
     return DCFM_OK;
@@ -138,18 +147,25 @@ int dcfm_get_sigma(dcfm_handle *h, double *out) { return sigma_moment(h, DCFM_SI
 int dcfm_get_sigma_moment(dcfm_handle *h, int32_t which, double *out) { return sigma_moment(h, which, out); }
 
 int dcfm_get_precision_mean_cols(dcfm_handle *h, int64_t col0, int64_t ncols, double *out) {
-    return sigma_moment_cols(h, DCFM_SIGMA_MEAN, col0, ncols, out, true);
+    return sigma_moment_cols(h, DCFM_SIGMA_MEAN, col0, ncols, out, SRC_PREC);
 }
 
-int dcfm_get_precision_mean(dcfm_handle *h, double *out) { return sigma_moment(h, DCFM_SIGMA_MEAN, out, true); }
+int dcfm_get_precision_mean(dcfm_handle *h, double *out) { return sigma_moment(h, DCFM_SIGMA_MEAN, out, SRC_PREC); }
+
+int dcfm_get_partial_corr_cols(dcfm_handle *h, int32_t which, int64_t col0, int64_t ncols, double *out) {
+    return sigma_moment_cols(h, which, col0, ncols, out, SRC_PCORR);
+}
+
+int dcfm_get_partial_corr(dcfm_handle *h, int32_t which, double *out) { return sigma_moment(h, which, out, SRC_PCORR); }
 
 int dcfm_sigma_block(const dcfm_handle *h, int64_t out[3]) {
     if (!h || !out) return fail(nullptr, DCFM_ERR_INVALID, "null argument");
     const int64_t p = h->d.p;
     out[0] = std::min<int64_t>(p, (int64_t)h->b.T0 * ASM_TILE);
     out[1] = std::min<int64_t>(p, (int64_t)h->b.T1 * ASM_TILE);
+    // beside the mean: the second moment, the precision mean, the two moments of the partial correlations
     out[2] = (int64_t)(tri(h->b.T1) - tri(h->b.T0)) * ASM_TILE * ASM_TILE * (int64_t)sizeof(double) *
-             (1 + (h->b.Sigma2 ? 1 : 0) + (h->pm.Prec ? 1 : 0));   // the second moment, the precision mean beside the mean
+             (1 + (h->b.Sigma2 ? 1 : 0) + (h->pm.Prec ? 1 : 0) + (h->pc.PC ? 2 : 0));
     return DCFM_OK;
 }
 

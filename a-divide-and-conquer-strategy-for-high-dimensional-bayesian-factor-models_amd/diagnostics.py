@@ -195,3 +195,20 @@ def partial_correlations(T) -> np.ndarray:
         R = -T / (s[:, None] * s[None, :])
     R[np.diag_indices_from(R)] = np.where(d > 0, 1.0, np.nan)
     return R
+
+
+def partial_correlation_edges(mean, sd, z=1.96, min_abs=0.0) -> dict:
+    """Edges of the graphical model from the posterior mean and standard deviation of the partial
+    correlations (``Sampler.get_partial_corr("mean")`` / ``("sd")``, or ``divideconquer(..., return_partial=True)``).
+    Returns ``{"z": |mean| / sd, "edges": bool p x p}``: ``z`` is inf where sd == 0 and mean != 0, and NaN where
+    either input is NaN or both are 0; ``edges[a, b]`` holds where ``|mean| >= min_abs`` and ``z-score >= z``
+    on the pair (a, b) *and* on (b, a), so it is symmetric; its diagonal is False, and a NaN is no edge."""
+    mean, sd = np.asarray(mean, dtype=np.float64), np.asarray(sd, dtype=np.float64)
+    if mean.ndim != 2 or mean.shape[0] != mean.shape[1] or sd.shape != mean.shape:
+        raise ValueError(f"mean and sd must both be p x p, got {mean.shape} and {sd.shape}")
+    with np.errstate(divide="ignore", invalid="ignore"):
+        zs = np.abs(mean) / sd
+        e = (np.abs(mean) >= min_abs) & (zs >= z)
+    e = e & e.T
+    e[np.diag_indices_from(e)] = False
+    return {"z": zs, "edges": e}

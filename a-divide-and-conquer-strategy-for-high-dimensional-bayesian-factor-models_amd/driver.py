@@ -205,7 +205,7 @@ def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hy
                   init_draws=None, iter_draws=None, nranks=1, rank=0, device=0, comm_uid=None,
                   asm_batch=0, return_info=False, device_ingest=True, device_init=True, return_sd=False,
                   n_components=0, rhs=None, probes=None, precision_probes=None, return_precision=False, loglik=False,
-                  predict=None, impute=False):
+                  predict=None, impute=False, return_partial=False):
     """Sigmaout = divideconquer(Y,g,k,BURNIN,MCMC,thin,rho)   (divideconquer.m:1).
 
     ``device_ingest`` (default): the zero-column scan and the partition/standardisation
@@ -228,6 +228,14 @@ def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hy
     coordinates; E[inv(Sigma)], not the inverse of Sigmaout -- to the returned tuple after Sigmasd (if
     requested) and before the ``n_components`` dict.  ``unpermute_precision`` takes it back to the input's
     column order and ``diagnostics.partial_correlations`` reads the partial correlations off it.
+
+    ``return_partial``: also accumulate the posterior mean and second moment of the per-sample partial
+    correlations on the device (DCFM_FLAG_PARTIAL_CORR) and append ``{"mean", "sd"}`` after Theta (if requested)
+    and before the ``n_components`` dict: the posterior mean (with Sigmaout's 1/effsamp scaling, quirk Q8: its diagonal is
+    saved/effsamp, 1 when thin divides MCMC and BURNIN) and the posterior standard deviation of every partial correlation, p_orig x p_orig in the *input's* column order
+    (``unpermute_partial``: partial correlations do not change with the columns' scaling, so this is a pure
+    un-permutation; dropped all-zero columns get NaN, with 1 (mean) and 0 (sd) on the diagonal).
+    ``diagnostics.partial_correlation_edges`` turns the pair into the edges of the graphical model.
 
     ``n_components`` > 0: also the leading principal components of Sigmaout, found on the device
     (Sampler.sigma_eigs: ``values``, ``vectors`` p x n_components, ``resid``, ``passes``,
@@ -334,7 +342,7 @@ def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hy
     s0 = rank * gl
     smp = Sampler(n, P, g, K, rho, BURNIN, MCMC, thin, hyper=hyper, seed=seed, nranks=nranks,
                   rank=rank, device=device, inject_draws=iter_draws is not None, asm_batch=asm_batch,
-                  sigma_m2=return_sd, precision_mean=return_precision)
+                  sigma_m2=return_sd, precision_mean=return_precision, partial_corr=return_partial)
     try:
         if nranks > 1:
             if comm_uid is None:
@@ -367,6 +375,12 @@ def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hy
         Sigmaout = smp.get_sigma()
         Sigmasd = smp.get_sigma_moment("sd") if return_sd else None
         Theta = smp.get_precision_mean() if return_precision else None
+        pcr = None
+        if return_partial:
+            Rm, Rs = smp.get_partial_corr("mean"), smp.get_partial_corr("sd")
+            if Rm is not None:                                   # rank 0
+                pcr = {"mean": unpermute_partial(Rm, keep, init.varind, np.asarray(Y).shape[1]),
+                       "sd": unpermute_partial(Rs, keep, init.varind, np.asarray(Y).shape[1], diag=0.0)}
         pcs = smp.sigma_eigs(int(n_components)) if n_components > 0 else None
         sol = None
         if rhs is not None:
@@ -403,6 +417,8 @@ def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hy
     out = (Sigmaout, Sigmasd) if return_sd else (Sigmaout,)
     if return_precision:
         out += (Theta,)
+    if return_partial:
+        out += (pcr,)
     if n_components > 0:
         out += (pcs,)
     if rhs is not None:
@@ -519,6 +535,21 @@ def unpermute_precision(T, keep, varind, p_orig, sd=None, fill=0.0):
         T = T / sd[:, None] / sd[None, :]
     out = np.full((p_orig, p_orig), fill, dtype=np.float64)
     out[np.ix_(cols, cols)] = T
+    return out
+
+
+def unpermute_partial(R, keep, varind, p_orig, fill=np.nan, diag=1.0):
+    """A partial-correlation matrix in Sigmaout's coordinates (``Sampler.get_partial_corr``, or
+    ``diagnostics.partial_correlations`` of a precision matrix) back in the input's column order: R[a, b] goes
+    to (cols[a], cols[b]) with cols = output_columns(keep, varind).  Partial correlations are invariant to
+    the columns' scaling -- (D T D)_ab / sqrt((D T D)_aa (D T D)_bb) = T_ab / sqrt(T_aa T_bb) for a positive
+    diagonal D -- so, unlike ``unpermute_sigma`` and ``unpermute_precision``, there is no ``sd``: a pure
+    un-permutation.  Rows/columns of dropped (all-zero, dc:36-39) columns get ``fill`` (NaN: the model says
+    nothing about them) with ``diag`` on their diagonal (1, a variable with itself; pass 0 for a matrix of
+    standard deviations)."""
+    out = unpermute_sigma(R, keep, varind, p_orig, fill=fill)
+    dropped = np.setdiff1d(np.arange(p_orig), output_columns(keep, varind))
+    out[dropped, dropped] = diag
     return out
 
 

@@ -76,6 +76,13 @@ extern "C" {
                                         buffer and the kernels of precision_mean.hip per flush), for
                                         dcfm_get_precision_mean[_cols]; off: nothing is allocated or
                                         launched                                          */
+#define DCFM_FLAG_PARTIAL_CORR 0x200u  /* also accumulate the posterior mean and second moment of the
+                                        per-sample partial correlations (two more buffers the size of
+                                        this rank's Sigmaout block; the per-sample omega slots, factor
+                                        buffer and panel kernels it shares with PRECISION_MEAN, plus the
+                                        kernels of partial_corr.hip per flush), for
+                                        dcfm_get_partial_corr[_cols]; off: nothing is allocated or
+                                        launched                                          */
 
 typedef struct dcfm_handle dcfm_handle;
 
@@ -206,7 +213,8 @@ int  dcfm_get_sigma_cols(dcfm_handle *h, int64_t col0, int64_t ncols, double *ou
  * triangle it accumulates (contiguous 128-row tiles, balanced by tile count over
  * the ranks), out[2] = its device bytes for Sigmaout (~p^2 / (2 nranks) * 8; once more
  * with DCFM_FLAG_SIGMA_M2, the second moment beside the mean, and once more with
- * DCFM_FLAG_PRECISION_MEAN, the precision accumulator). */
+ * DCFM_FLAG_PRECISION_MEAN, the precision accumulator, and twice more with
+ * DCFM_FLAG_PARTIAL_CORR, the two moments of the partial correlations). */
 int  dcfm_sigma_block(const dcfm_handle *h, int64_t out[3]);
 int64_t dcfm_saved_samples(const dcfm_handle *h);
 /* Posterior moments of Sigma's entries.  With Sigma(s) the matrix dc:182-192 builds from saved
@@ -236,6 +244,30 @@ int  dcfm_get_sigma_moment(dcfm_handle *h, int32_t which, double *out);
  * striping and collective semantics as dcfm_get_sigma_cols / dcfm_get_sigma. */
 int  dcfm_get_precision_mean_cols(dcfm_handle *h, int64_t col0, int64_t ncols, double *out);
 int  dcfm_get_precision_mean(dcfm_handle *h, double *out);
+/* Posterior moments of the partial correlations (DCFM_FLAG_PARTIAL_CORR at dcfm_create, else
+ * DCFM_ERR_INVALID).  With Theta(s) = Sigma(s)^-1 of saved sample s (Sigma(s) the per-sample matrix of
+ * dc:182-192) and d_a(s) = Theta(s)_aa, the per-sample partial-correlation matrix is
+ *   R(s)_ab = -Theta(s)_ab / sqrt(d_a(s) d_b(s))  (a != b),   R(s)_aa = 1 exactly,
+ * and `which` selects
+ *   DCFM_SIGMA_MEAN  PC  = (1/effsamp) sum_s R(s), with the same effsamp = mcmc/thin scaling (quirk Q8)
+ *                    as Sigmaout: its diagonal is exactly 1 * saved / effsamp (the count of the saved
+ *                    samples scaled, not a computed product);
+ *   DCFM_SIGMA_M2    PC2 = (1/effsamp) sum_s R(s).^2, the same scaling;
+ *   DCFM_SIGMA_SD    sqrt(max(0, r PC2 - (r PC).^2)), r = effsamp / dcfm_saved_samples(h): the posterior
+ *                    standard deviation (population form) over the samples saved so far; 0 on the diagonal.
+ * R(s) is not linear in Sigma(s)^-1: PC is the posterior mean of the partial correlation, not the plug-in
+ * -T_ab / sqrt(T_aa T_bb) of the precision mean T, and the SD is what tells an edge of the graphical model
+ * from noise.  All zeros before the first saved sample; SD with no saved sample and a `which` outside the
+ * three are DCFM_ERR_INVALID.  Accumulated on the device tile by tile from the thin factor panels of
+ * Sigma(s)^-1, each row scaled by 1 / sqrt(d_a(s)) (a non-positive d_a(s) gives NaN, which runs through):
+ * an entry of R(s) is accurate to first order in eps cond(Sigma(s)), and |R(s)_ab| <= 1.  M2 - mean^2
+ * cancels: an entry's variance keeps about eps PC2 / var relative accuracy.  Device bytes: twice this
+ * rank's Sigmaout block (dcfm_sigma_block), plus -- shared with DCFM_FLAG_PRECISION_MEAN, whose accumulator
+ * is not allocated for this flag alone -- the factor buffer p x 4 round_up(asm_batch K, 16) doubles, the
+ * (2 g + 1) asm_batch K^2 scratch and the omega slots 2 p asm_batch.  p x p in Sigmaout's coordinates,
+ * symmetric bit for bit; layout, striping and collective semantics as dcfm_get_sigma_moment[_cols]. */
+int  dcfm_get_partial_corr_cols(dcfm_handle *h, int32_t which, int64_t col0, int64_t ncols, double *out);
+int  dcfm_get_partial_corr(dcfm_handle *h, int32_t which, double *out);
 /* Error of Sigmaout against a truth Sigma0 = U U' + diag(s) given in the same permuted,
  * standardised coordinates (U: p x r column-major, r <= 32; s: p), computed on the
  * device (Sigmaout never leaves HBM; c5: 80 GB).  out[0] = ||Sigmaout - Sigma0||_F,

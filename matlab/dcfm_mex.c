@@ -7,7 +7,7 @@
  * on the GPU).  Commands:
  *   h = dcfm_mex('create', cfg)           cfg fields n P g K rho burnin mcmc thin as bs df ad1
  *                                         bd1 ad2 bd2 seed device inject asm_batch sigma_m2
- *                                         precision_mean
+ *                                         precision_mean partial_corr
  *   dcfm_mex('set_data', h, Yd)           Yd n x P x g (dc:49-59 done by the caller)
  *   dcfm_mex('set_data_raw', h, Y0, cols) raw n x p0 data + int64 0-based columns (dc:48-59 on GPU)
  *   dcfm_mex('set_state', h, Lambda, ps, omega, psijh, Plam, X, Z, delta, tauh)
@@ -25,6 +25,11 @@
  *                                         (1/effsamp) * sum over the saved samples of inv(Sigma_s) (needs
  *                                         cfg.precision_mean = 1), p x p or the columns col0 .. col0+ncols-1
  *                                         (0-based), p x ncols; Sigmaout's coordinates
+ *   R = dcfm_mex('partial_corr', h, which[, col0, ncols])   which = 'mean' | 'm2' | 'sd': posterior mean,
+ *                                         second moment or standard deviation of the partial correlations
+ *                                         -T_ab / sqrt(T_aa * T_bb), T = inv(Sigma_s), over the saved samples
+ *                                         (needs cfg.partial_corr = 1), p x p or the columns col0 ..
+ *                                         col0+ncols-1 (0-based), p x ncols; Sigmaout's coordinates
  *   Y = dcfm_mex('sigma_apply', h, V)     Y = Sigmaout * V on the device, V p x nv (any nv >= 1), in
  *                                         Sigmaout's permuted, standardised coordinates
  *   [d, V, res] = dcfm_mex('sigma_eigs', h, r[, tol, max_passes, seed])   the r <= 32 largest eigenpairs
@@ -155,6 +160,7 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         c.flags = fld(s, "inject", 0) != 0 ? DCFM_FLAG_INJECT_DRAWS : 0u;
         if (fld(s, "sigma_m2", 0) != 0) c.flags |= DCFM_FLAG_SIGMA_M2;
         if (fld(s, "precision_mean", 0) != 0) c.flags |= DCFM_FLAG_PRECISION_MEAN;
+        if (fld(s, "partial_corr", 0) != 0) c.flags |= DCFM_FLAG_PARTIAL_CORR;
         c.asm_batch = (int32_t)fld(s, "asm_batch", 0);
         int i = 0;
         while (i < NSLOT && S[i].h) ++i;
@@ -293,7 +299,8 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
                               (long long)p);
         plhs[0] = mxCreateDoubleMatrix((mwSize)p, (mwSize)p, mxREAL);
         ck(t->h, dcfm_get_sigma(t->h, mxGetDoubles(plhs[0])));
-    } else if (!strcmp(cmd, "sigma_moment")) {       /* M = dcfm_mex('sigma_moment', h, which[, col0, ncols]) */
+    } else if (!strcmp(cmd, "sigma_moment") || !strcmp(cmd, "partial_corr")) {
+        /* M = dcfm_mex('sigma_moment', h, which[, col0, ncols]), R = dcfm_mex('partial_corr', h, which[, col0, ncols]) */
         if (nrhs != 3 && nrhs != 5)
             mexErrMsgIdAndTxt("dcfm:nargs", "'%s' takes 2 or 4 arguments, got %d", cmd, nrhs - 1);
         /* the arguments that need no handle first: a malformed call never reaches the library */
@@ -318,7 +325,10 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         if (c0 + nc > (double)p)
             mexErrMsgIdAndTxt("dcfm:arg", "columns [%g, %g) outside 0..p = %lld", c0, c0 + nc, (long long)p);
         plhs[0] = mxCreateDoubleMatrix((mwSize)p, (mwSize)nc, mxREAL);
-        ck(t->h, dcfm_get_sigma_moment_cols(t->h, which, (int64_t)c0, (int64_t)nc, mxGetDoubles(plhs[0])));
+        if (!strcmp(cmd, "partial_corr"))
+            ck(t->h, dcfm_get_partial_corr_cols(t->h, which, (int64_t)c0, (int64_t)nc, mxGetDoubles(plhs[0])));
+        else
+            ck(t->h, dcfm_get_sigma_moment_cols(t->h, which, (int64_t)c0, (int64_t)nc, mxGetDoubles(plhs[0])));
     } else if (!strcmp(cmd, "precision_mean")) {     /* T = dcfm_mex('precision_mean', h[, col0, ncols]) */
         if (nrhs != 2 && nrhs != 4)
             mexErrMsgIdAndTxt("dcfm:nargs", "'%s' takes 1 or 3 arguments, got %d", cmd, nrhs - 1);

@@ -38,6 +38,12 @@ def state_dict(st, s0=0, gl=None):
     return out
 
 
+def as_oracle_state(st):
+    """The oracle's SamplerState of a device state (Sampler.get_state: every STATE_CMP field, MATLAB
+    layout), to restart the oracle from it."""
+    return oracle.SamplerState(**{f: np.array(v, dtype=np.float64, order="F") for f, v in st.items()})
+
+
 def stacked_draws(src, first, n_iter):
     ds = [src.iteration(t) for t in range(first, first + n_iter)]
     return ds[0].stacked(ds[1:])

@@ -31,8 +31,8 @@ reference's own algebra ends -- chol of a loading system that is no longer posit
 import numpy as np
 import pytest
 
-from helpers import (STATE_CMP, make_case, rel_err, residual_rounding_bound, scaled_rel_err, stacked_draws,
-                     stagewise_errors, state_dict)
+from helpers import (STATE_CMP, as_oracle_state as _as_oracle, make_case, rel_err, residual_rounding_bound,
+                     scaled_rel_err, stacked_draws, stagewise_errors, state_dict)
 
 pytestmark = pytest.mark.gpu
 
@@ -64,11 +64,6 @@ def _excursion_states(dcfm, c, g, K, seeds=(11, 4, 22), iters=400, chunk=10, xmi
         if found:
             return sorted(found, key=lambda st: -float(np.abs(st["X"]).max()))
     return []
-
-
-def _as_oracle(st):
-    from oracle import SamplerState
-    return SamplerState(**{f: np.array(v, dtype=np.float64, order="F") for f, v in st.items()})
 
 
 def test_fused_run_in_x_excursion_regime(dcfm, record_property):

@@ -45,9 +45,27 @@ def _draws(dcfm, seed, n, P, g, K, first, T, hyper):
     return dict(NZ=NZ, NX=NX, NL=NL, Gpsi=Gpsi, Gdelta=Gdelta, Gps=Gps)
 
 
+UNFUSED = 0x2     # include/dcfm.h: the side-stream layout at K <= 32, whose kernels read the k_draws buffers
+
+# both sides of draw_plan's lane steps (csrc/draws.h: lanes_for(K) at K = 16 / 17, lanes_for(ceil(K / 2)) at
+# 64 / 65; 32 / 33 are the K = 32 and K = 40 cases) and the loading-row classes k_lambda<24> and
+# k_lambda_w<128, 6> (tests/k_paths.py); P = 21 and 37 leave the last k_draws row-block partial
+LANE_STEP_CASES = [(40, 42, 2, 16), (40, 42, 2, 17), (40, 63, 3, 23), (90, 74, 2, 65), (120, 74, 2, 89)]
+
+
 @pytest.mark.parametrize("n,p,g,K", [(40, 60, 4, 5), (50, 96, 8, 30), (36, 64, 2, 32), (44, 80, 4, 20), (30, 52, 4, 13),
-                                     (80, 96, 4, 40), (150, 128, 2, 100)])
+                                     (80, 96, 4, 40), (150, 128, 2, 100)] + LANE_STEP_CASES)
 def test_generated_equals_injected_at_the_counters(dcfm, n, p, g, K):
+    _generated_vs_injected(dcfm, n, p, g, K, 0)
+
+
+@pytest.mark.parametrize("n,p,g,K", [c for c in LANE_STEP_CASES if c[3] <= 32])
+def test_generated_equals_injected_unfused(dcfm, n, p, g, K):
+    """The same under DCFM_FLAG_UNFUSED, where the K <= 32 sweep reads k_draws' buffers."""
+    _generated_vs_injected(dcfm, n, p, g, K, UNFUSED)
+
+
+def _generated_vs_injected(dcfm, n, p, g, K, flags):
     seed, burnin, mcmc, thin = 77, 1, 3, 1
     N = burnin + mcmc
     c = make_case(n, p, g, K, seed=9)
@@ -55,7 +73,8 @@ def test_generated_equals_injected_at_the_counters(dcfm, n, p, g, K):
     st = {f: v for f, v in state_dict(c["st"]).items() if f != "eta"}
     out = []
     for inject in (False, True):
-        smp = dcfm.Sampler(c["n"], P, g, K, c["rho"], burnin, mcmc, thin, seed=seed, inject_draws=inject)
+        smp = dcfm.Sampler(c["n"], P, g, K, c["rho"], burnin, mcmc, thin, seed=seed, inject_draws=inject,
+                           flags=flags)
         try:
             smp.set_data(c["Yd"])
             smp.set_state(st)

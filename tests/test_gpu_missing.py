@@ -29,7 +29,7 @@ import numpy as np
 import pytest
 
 import missing_cases as mc
-from helpers import make_case, rel_err, stacked_draws, stagewise_errors, state_dict
+from helpers import as_oracle_state as _as_oracle, make_case, rel_err, stacked_draws, stagewise_errors, state_dict
 
 pytestmark = pytest.mark.gpu
 
@@ -94,11 +94,6 @@ def _open(dcfm, name, mask, *, flags=0, burnin=0, mcmc=RN, thin=1, asm_batch=0, 
         smp.close()
         raise
     return smp
-
-
-def _as_oracle(st):
-    from oracle import SamplerState
-    return SamplerState(**{f: np.array(v, dtype=np.float64, order="F") for f, v in st.items()})
 
 
 def _stepped(dcfm, name, pattern, flags=0):

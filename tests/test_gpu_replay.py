@@ -21,7 +21,7 @@ import numpy as np
 import pytest
 
 import replay_cases as rc
-from helpers import STATE_CMP, residual_rounding_bound, scaled_rel_err, stagewise_errors
+from helpers import STATE_CMP, as_oracle_state as _as_oracle, residual_rounding_bound, scaled_rel_err, stagewise_errors
 
 pytestmark = pytest.mark.gpu
 
@@ -76,11 +76,6 @@ def _assert_state_equal(got, want, what):
     assert set(got) == set(want) == set(STATE_CMP)              # every STATE_FIELDS member
     for f in want:
         assert np.array_equal(got[f], want[f]), f"{what}: {f} not bitwise equal"
-
-
-def _as_oracle(st):
-    from oracle import SamplerState
-    return SamplerState(**{f: np.array(v, dtype=np.float64, order="F") for f, v in st.items()})
 
 
 # ---- (a) -------------------------------------------------------------------------------------------

@@ -12,8 +12,8 @@ Import through the repo-root helper (the directory name has hyphens)::
 from ._abi import DcfmError, load_library, EXPORTS, LIB_PATH
 from .sampler import Hyper, Sampler, rng_fill, count_nonzero_columns, STATE_FIELDS
 from . import diagnostics
-from .diagnostics import heldout_log_density, summarize_probes, partial_correlations, partial_correlation_edges, waic, conditional_log_density
-from .driver import divideconquer, preprocess, preprocess_device, shard_columns, partition_standardize, initial_state, local_state, truth_factors, output_columns, unpermute_sigma, unpermute_vectors, permute_vectors, unpermute_precision, unpermute_partial
+from .diagnostics import heldout_log_density, summarize_probes, partial_correlations, partial_correlation_edges, correlation, waic, conditional_log_density
+from .driver import divideconquer, preprocess, preprocess_device, shard_columns, partition_standardize, initial_state, local_state, truth_factors, output_columns, unpermute_sigma, unpermute_vectors, permute_vectors, unpermute_precision, unpermute_partial, unpermute_corr, unpermute_communality
 from .driver import preprocess_missing, partition_standardize_missing, observed_moments, unstandardize_imputation
 
 __all__ = [
@@ -23,5 +23,6 @@ __all__ = [
     "local_state", "truth_factors", "output_columns", "unpermute_sigma", "count_nonzero_columns",
     "preprocess_device", "shard_columns", "diagnostics", "unpermute_vectors", "permute_vectors",
     "summarize_probes",
-    "heldout_log_density", "unpermute_precision", "partial_correlations", "unpermute_partial", "partial_correlation_edges", "waic", "conditional_log_density",
+    "heldout_log_density", "unpermute_precision", "partial_correlations", "unpermute_partial", "partial_correlation_edges",
+    "correlation", "unpermute_corr", "unpermute_communality", "waic", "conditional_log_density",
 ]

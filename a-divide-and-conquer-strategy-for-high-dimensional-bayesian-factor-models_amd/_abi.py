@@ -30,7 +30,8 @@ DCFM_FLAG_GUARD_ALL = 0x40       # the SS-identity guard rejects every row (its 
 DCFM_FLAG_SIGMA_M2 = 0x80        # accumulate the second moment of the per-sample Sigma (M2 / SD read-out)
 DCFM_FLAG_PRECISION_MEAN = 0x100  # accumulate the posterior mean of the per-sample Sigma^-1 (get_precision_mean)
 DCFM_FLAG_PARTIAL_CORR = 0x200    # accumulate the mean and second moment of the per-sample partial correlations
-# dcfm_get_sigma_moment[_cols]'s and dcfm_get_partial_corr[_cols]'s `which`
+DCFM_FLAG_CORR = 0x400            # accumulate the mean and second moment of the per-sample correlations and communalities
+# `which` of dcfm_get_sigma_moment[_cols], dcfm_get_partial_corr[_cols], dcfm_get_corr[_cols], dcfm_get_communality
 DCFM_SIGMA_MEAN = 0
 DCFM_SIGMA_M2 = 1
 DCFM_SIGMA_SD = 2
@@ -56,6 +57,7 @@ EXPORTS = (
     "dcfm_sigma_solve", "dcfm_set_probes", "dcfm_get_probe_draws", "dcfm_set_precision_probes",
     "dcfm_get_precision_draws", "dcfm_get_precision_mean_cols", "dcfm_get_precision_mean",
     "dcfm_get_partial_corr_cols", "dcfm_get_partial_corr",
+    "dcfm_get_corr_cols", "dcfm_get_corr", "dcfm_get_communality",
     "dcfm_set_loglik", "dcfm_get_loglik", "dcfm_set_predict", "dcfm_get_predict",
     "dcfm_set_missing", "dcfm_get_imputed",
 )
@@ -130,6 +132,9 @@ def load_library(path: Path | None = None):
         "dcfm_get_precision_mean": (C.c_int, [vp, _DP]),
         "dcfm_get_partial_corr_cols": (C.c_int, [vp, C.c_int32, C.c_int64, C.c_int64, _DP]),
         "dcfm_get_partial_corr": (C.c_int, [vp, C.c_int32, _DP]),
+        "dcfm_get_corr_cols": (C.c_int, [vp, C.c_int32, C.c_int64, C.c_int64, _DP]),
+        "dcfm_get_corr": (C.c_int, [vp, C.c_int32, _DP]),
+        "dcfm_get_communality": (C.c_int, [vp, C.c_int32, _DP]),
         "dcfm_saved_samples": (C.c_int64, [vp]),
         "dcfm_sigma_error": (C.c_int, [vp, _DP, C.c_int32, _DP, C.c_int32, C.c_uint64, _DP]),
         "dcfm_sigma_apply": (C.c_int, [vp, _DP, C.c_int32, _DP, _DP]),

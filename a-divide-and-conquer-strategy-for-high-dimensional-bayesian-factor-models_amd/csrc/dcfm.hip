@@ -256,7 +256,15 @@ static int alloc_buffers(dcfm_handle *h) {
         TRY(dalloc(h, &pm.pscr, precision_mean_scratch_doubles(d.g, d.K, h->B)));
         HIPC(h, precision_mean_setup());
     }
-    if (c.flags & (DCFM_FLAG_SIGMA_M2 | DCFM_FLAG_PRECISION_MEAN | DCFM_FLAG_PARTIAL_CORR)) {   // each saved sample's own omega
+    if (c.flags & DCFM_FLAG_CORR) {             // mean and second moment of the per-sample correlations and communalities
+        Corr &cr = h->cr;
+        TRY(dalloc(h, &cr.C, (size_t)(tri(b.T1) - tri(b.T0)) * ASM_TILE * ASM_TILE));
+        TRY(dalloc(h, &cr.C2, (size_t)(tri(b.T1) - tri(b.T0)) * ASM_TILE * ASM_TILE));
+        TRY(dalloc(h, &cr.cscale, p * (size_t)h->B));
+        TRY(dalloc(h, &cr.H, p));
+        TRY(dalloc(h, &cr.H2, p));
+    }
+    if (c.flags & (DCFM_FLAG_SIGMA_M2 | DCFM_FLAG_PRECISION_MEAN | DCFM_FLAG_PARTIAL_CORR | DCFM_FLAG_CORR)) {   // each saved sample's own omega
         TRY(dalloc(h, &b.wslot[0], p * (size_t)h->B));
         TRY(dalloc(h, &b.wslot[1], p * (size_t)h->B));
     }
@@ -421,6 +429,8 @@ static int flush_batch(dcfm_handle *h) {
         if (h->pm.Prec) launch_precision_mean(d, b, h->pm, b.wslot[lb], h->batch, h->B, 1.0 / effsamp, h->sasm);
         // DCFM_FLAG_PARTIAL_CORR: the panels scaled in place, the partial correlations into their two moments
         if (h->pc.PC) launch_partial_corr(d, b, h->pm, h->pc, b.wslot[lb], h->batch, h->B, 1.0 / effsamp, h->sasm);
+        // DCFM_FLAG_CORR: the rows' scales and communalities, the per-sample correlations into their two moments
+        if (h->cr.C) launch_corr(d, b, h->cr, b.Lb[lb], b.wslot[lb], h->batch, h->B, 1.0 / effsamp, h->sasm);
     }
     HIPC(h, hipGetLastError());
     HIPC(h, hipMemsetAsync(b.wsum[lb], 0, (size_t)d.p * sizeof(double), h->sasm));   // k_save adds into it

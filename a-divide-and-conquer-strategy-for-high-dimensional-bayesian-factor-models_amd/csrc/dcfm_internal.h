@@ -23,12 +23,15 @@
 //   sloc   [G][KW], sall [g][KW]  column sums (all-gathered)
 //   Lb     [2][p][LDB]   saved Lambda rows of an assembly batch (double-buffered), sample s at cols s*K..
 //   wsum   [2][p]        sum of saved omega of the batch
-//   wslot  [2][p][B]     DCFM_FLAG_SIGMA_M2 / _PRECISION_MEAN / _PARTIAL_CORR: each saved sample's own omega (slot s of row a at a*B + s)
+//   wslot  [2][p][B]     DCFM_FLAG_SIGMA_M2 / _PRECISION_MEAN / _PARTIAL_CORR / _CORR: each saved sample's own omega (slot s of row a at a*B + s)
 //   Prec   [ntiles][128][128]  DCFM_FLAG_PRECISION_MEAN: mean of the per-sample Sigma^{-1}, laid out as Sigma
 //   pfac   [p][4 KH]     DCFM_FLAG_PRECISION_MEAN / _PARTIAL_CORR: the factor panels of a flush (precision_mean.hip), KH = round_up(B K, 16);
 //                        pscr [(2 g + 1) B][K][K] the shards' H_m, B_m^{-1} and the slots' S^{-1}
 //   PC, PC2 [ntiles][128][128]  DCFM_FLAG_PARTIAL_CORR: mean and second moment of the per-sample partial
 //                        correlations, laid out as Sigma (partial_corr.hip; it shares pfac, pscr, wslot)
+//   C, C2  [ntiles][128][128]  DCFM_FLAG_CORR: mean and second moment of the per-sample correlation matrix, laid
+//                        out as Sigma (corr.hip); cscale [p][B] the rows' 1 / sqrt(Sigma(s)_aa) of a flush,
+//                        H, H2 [p] mean and second moment of the communalities
 //   Sigma2 [ntiles][128][128]  DCFM_FLAG_SIGMA_M2: second moment of the per-sample Sigma, laid out as Sigma
 //   Sigma  [ntiles][128][128]  this rank's block of the lower triangle of Sigmaout, tile-packed:
 //                        rank r owns the contiguous tile rows [T0, T1) (balanced by tile count,
@@ -243,6 +246,12 @@ struct PrecMean {
 struct PartialCorr {
     double *PC, *PC2;
 };
+// Marginal correlations and communalities (corr.hip, DCFM_FLAG_CORR; all null when off): C the mean and C2 the
+// second moment of the per-sample R(s), both laid out as Bufs::Sigma; cscale [p][B] the scales of a flush;
+// H, H2 [p] the two moments of the communalities (all p rows on every rank)
+struct Corr {
+    double *C, *C2, *cscale, *H, *H2;
+};
 // Bufs::sync: [0] the X operators (k_xdraw, several ranks), [1] spare, [2, 2 + 256) chunk counters of the A sum, [SYNC_ZM, SYNC_ZM + G) the
 // per-shard Z-operator counters (the fused W pass draws Z once its shard's operators are out)
 constexpr int SYNC_ZM = 2 + 256;
@@ -355,6 +364,10 @@ void launch_pc_mean(const Dims &d, const Bufs &b, const PrecMean &pm, int nslots
 // pc.PC += (1 / effsamp) sum_s R(s) and pc.PC2 += (1 / effsamp) sum_s R(s).^2 over the batch's nslots samples
 void launch_partial_corr(const Dims &d, const Bufs &b, const PrecMean &pm, const PartialCorr &pc, const double *wslot,
                          int nslots, int B, double inv_eff, hipStream_t s);
+// corr.hip, on the assembly stream: cr.cscale and cr.H / cr.H2 of the batch's nslots samples (k_corr_scale), then
+// cr.C += (1 / effsamp) sum_s R(s) and cr.C2 += (1 / effsamp) sum_s R(s).^2 (k_corr); Lb and wslot are only read
+void launch_corr(const Dims &d, const Bufs &b, const Corr &cr, const double *Lb, const double *wslot, int nslots,
+                 int B, double inv_eff, hipStream_t s);
 // column stripe [c0, c0 + nc) of Sigmaout from a rank's tile-packed block (tile rows [T0, T1)):
 // the rank's packed windows (win_lo / win_off; with one rank = the dense p x nc stripe).
 // which (DCFM_SIGMA_*): 0 the mean S, 1 the second moment S2, 2 sqrt(max(0, rs S2 - (rs S)^2)).

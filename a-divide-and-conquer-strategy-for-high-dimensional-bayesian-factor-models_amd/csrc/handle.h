@@ -97,6 +97,8 @@ struct dcfm_handle {
     PrecMean pm{};
     // posterior mean and second moment of the partial correlations (DCFM_FLAG_PARTIAL_CORR, partial_corr.hip)
     PartialCorr pc{};
+    // posterior mean and second moment of the correlation matrix and of the communalities (DCFM_FLAG_CORR, corr.hip)
+    Corr cr{};
     bool prof = false;
     uint32_t prof_mask = 0;       // kernel ids (bit DCFM_K_*) timed with events
     int prof_stride = 1;          // time one in prof_stride launches of each (dcfm_set_profiling_stride)

@@ -6,11 +6,14 @@
 // root rank: the one body of dcfm_get_sigma_cols (the mean) and dcfm_get_sigma_moment_cols.  The
 // moments differ only in what k_sigma_pack reads from the rank's block(s).
 // src: the same read-out pointed at the precision mean (SRC_PREC: dcfm_get_precision_mean_cols; which =
-// DCFM_SIGMA_MEAN) or at the two moments of the partial correlations (SRC_PCORR: dcfm_get_partial_corr_cols).
-enum MomentSrc { SRC_SIGMA = 0, SRC_PREC, SRC_PCORR };
+// DCFM_SIGMA_MEAN), at the two moments of the partial correlations (SRC_PCORR: dcfm_get_partial_corr_cols) or at
+// those of the marginal correlations (SRC_CORR: dcfm_get_corr_cols).
+enum MomentSrc { SRC_SIGMA = 0, SRC_PREC, SRC_PCORR, SRC_CORR };
 static const char *const PCORR_FLAG_MSG = "the partial correlations need DCFM_FLAG_PARTIAL_CORR at dcfm_create";
+static const char *const CORR_FLAG_MSG = "the correlations and communalities need DCFM_FLAG_CORR at dcfm_create";
 static int sigma_moment_cols(dcfm_handle *h, int which, int64_t col0, int64_t ncols, double *out, MomentSrc src = SRC_SIGMA) {
-    const bool prec = src == SRC_PREC, pcorr = src == SRC_PCORR;
+    const bool prec = src == SRC_PREC, pcorr = src == SRC_PCORR, corr = src == SRC_CORR;
+    const bool unit = pcorr || corr;   // a unit diagonal per sample, and both moments of its own
     if (!h) return fail(h, DCFM_ERR_INVALID, "null handle");
     Dims &d = h->d;
     const int root = 0;
@@ -21,12 +24,13 @@ static int sigma_moment_cols(dcfm_handle *h, int which, int64_t col0, int64_t nc
     else if (prec && !h->pm.Prec)
         code = fail(h, DCFM_ERR_INVALID, "the precision mean needs DCFM_FLAG_PRECISION_MEAN at dcfm_create");
     else if (pcorr && !h->pc.PC) code = fail(h, DCFM_ERR_INVALID, "%s", PCORR_FLAG_MSG);
-    else if (!pcorr && which != DCFM_SIGMA_MEAN && !h->b.Sigma2)
+    else if (corr && !h->cr.C) code = fail(h, DCFM_ERR_INVALID, "%s", CORR_FLAG_MSG);
+    else if (!unit && which != DCFM_SIGMA_MEAN && !h->b.Sigma2)
         code = fail(h, DCFM_ERR_INVALID, "the second moment and the standard deviation of Sigma need "
                                          "DCFM_FLAG_SIGMA_M2 at dcfm_create");
     else if (which == DCFM_SIGMA_SD && h->saved < 1)
         code = fail(h, DCFM_ERR_INVALID, "standard deviation of %s: no saved sample yet",
-                    pcorr ? "the partial correlations" : "Sigma");
+                    pcorr ? "the partial correlations" : corr ? "the correlations" : "Sigma");
     else if (!out && d.rank == root) code = fail(h, DCFM_ERR_INVALID, "null output on the root rank");
     else if (col0 < 0 || ncols < 0 || col0 + ncols > d.p)
         code = fail(h, DCFM_ERR_INVALID, "columns [%lld, %lld) outside 0..p = %d", (long long)col0,
@@ -77,8 +81,10 @@ static int sigma_moment_cols(dcfm_handle *h, int which, int64_t col0, int64_t nc
     int rc = DCFM_OK;
     // R(s)_aa = 1 for every saved sample: the diagonal of both moments is the scaled count itself, its SD 0
     const double pdiag = which == DCFM_SIGMA_SD ? 0.0 : (double)h->saved / ((double)h->cfg.mcmc / (double)h->cfg.thin);
-    launch_sigma_pack(pcorr ? h->pc.PC : (prec ? h->pm.Prec : h->b.Sigma), pcorr ? h->pc.PC2 : h->b.Sigma2, which, rs, d.p,
-                      h->b.T0, h->b.T1, (int)col0, (int)ncols, mine, h->stream, pcorr ? &pdiag : nullptr);
+    const double *M1 = corr ? h->cr.C : pcorr ? h->pc.PC : prec ? h->pm.Prec : h->b.Sigma;
+    const double *M2 = corr ? h->cr.C2 : pcorr ? h->pc.PC2 : h->b.Sigma2;
+    launch_sigma_pack(M1, M2, which, rs, d.p, h->b.T0, h->b.T1, (int)col0, (int)ncols, mine, h->stream,
+                      unit ? &pdiag : nullptr);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) rc = fail(h, DCFM_ERR_HIP, "sigma_pack: %s", hipGetErrorString(e));
     double *dense = buf;   // one rank: its windows are the dense stripe
@@ -122,6 +128,7 @@ static int sigma_moment(dcfm_handle *h, int which, double *out, MomentSrc src = 
     if (src == SRC_PREC && !h->pm.Prec)
         return fail(h, DCFM_ERR_INVALID, "the precision mean needs DCFM_FLAG_PRECISION_MEAN at dcfm_create");
     if (src == SRC_PCORR && !h->pc.PC) return fail(h, DCFM_ERR_INVALID, "%s", PCORR_FLAG_MSG);
+    if (src == SRC_CORR && !h->cr.C) return fail(h, DCFM_ERR_INVALID, "%s", CORR_FLAG_MSG);
     if (!out && h->d.rank == 0) return fail(h, DCFM_ERR_INVALID, "null output on the root rank");
     const int64_t p = h->d.p;
     const int64_t chunk = std::max<int64_t>(32, std::min<int64_t>(p, ((int64_t)1 << 28) / p));
@@ -158,14 +165,50 @@ int dcfm_get_partial_corr_cols(dcfm_handle *h, int32_t which, int64_t col0, int6
 
 int dcfm_get_partial_corr(dcfm_handle *h, int32_t which, double *out) { return sigma_moment(h, which, out, SRC_PCORR); }
 
+int dcfm_get_corr_cols(dcfm_handle *h, int32_t which, int64_t col0, int64_t ncols, double *out) {
+    return sigma_moment_cols(h, which, col0, ncols, out, SRC_CORR);
+}
+
+int dcfm_get_corr(dcfm_handle *h, int32_t which, double *out) { return sigma_moment(h, which, out, SRC_CORR); }
+
+// Every rank holds all p communalities (k_corr_scale runs over the gathered batch): no collective, each rank
+// reads its own copy.  The SD is formed on the host from the two p-vectors.
+int dcfm_get_communality(dcfm_handle *h, int32_t which, double *out) {
+    if (!h) return fail(h, DCFM_ERR_INVALID, "null handle");
+    if (which != DCFM_SIGMA_MEAN && which != DCFM_SIGMA_M2 && which != DCFM_SIGMA_SD)
+        return fail(h, DCFM_ERR_INVALID, "communality moment %d: DCFM_SIGMA_MEAN, _M2 or _SD", which);
+    if (!h->cr.H) return fail(h, DCFM_ERR_INVALID, "%s", CORR_FLAG_MSG);
+    if (which == DCFM_SIGMA_SD && h->saved < 1)
+        return fail(h, DCFM_ERR_INVALID, "standard deviation of the communalities: no saved sample yet");
+    if (!out) return fail(h, DCFM_ERR_INVALID, "null output");
+    HIPC(h, hipSetDevice(h->cfg.device));
+    sync_all(h);
+    TRY(numeric_status(h));
+    const size_t p = (size_t)h->d.p;
+    if (which != DCFM_SIGMA_SD) {
+        HIPC(h, hipMemcpy(out, which == DCFM_SIGMA_MEAN ? h->cr.H : h->cr.H2, p * sizeof(double), hipMemcpyDeviceToHost));
+        return DCFM_OK;
+    }
+    std::vector<double> m2(p);
+    HIPC(h, hipMemcpy(out, h->cr.H, p * sizeof(double), hipMemcpyDeviceToHost));
+    HIPC(h, hipMemcpy(m2.data(), h->cr.H2, p * sizeof(double), hipMemcpyDeviceToHost));
+    const double rs = ((double)h->cfg.mcmc / (double)h->cfg.thin) / (double)h->saved;
+    for (size_t a = 0; a < p; ++a) {   // k_sigma_pack's form: sqrt(max(0, rs H2 - (rs H)^2))
+        const double m = rs * out[a];
+        out[a] = std::sqrt(std::fmax(0.0, std::fma(rs, m2[a], -m * m)));
+    }
+    return DCFM_OK;
+}
+
 int dcfm_sigma_block(const dcfm_handle *h, int64_t out[3]) {
     if (!h || !out) return fail(nullptr, DCFM_ERR_INVALID, "null argument");
     const int64_t p = h->d.p;
     out[0] = std::min<int64_t>(p, (int64_t)h->b.T0 * ASM_TILE);
     out[1] = std::min<int64_t>(p, (int64_t)h->b.T1 * ASM_TILE);
-    // beside the mean: the second moment, the precision mean, the two moments of the partial correlations
+    // beside the mean: the second moment, the precision mean, the two moments of the partial correlations and of
+    // the correlations
     out[2] = (int64_t)(tri(h->b.T1) - tri(h->b.T0)) * ASM_TILE * ASM_TILE * (int64_t)sizeof(double) *
-             (1 + (h->b.Sigma2 ? 1 : 0) + (h->pm.Prec ? 1 : 0) + (h->pc.PC ? 2 : 0));
+             (1 + (h->b.Sigma2 ? 1 : 0) + (h->pm.Prec ? 1 : 0) + (h->pc.PC ? 2 : 0) + (h->cr.C ? 2 : 0));
     return DCFM_OK;
 }
 

@@ -197,9 +197,29 @@ def partial_correlations(T) -> np.ndarray:
     return R
 
 
+def correlation(S) -> np.ndarray:
+    """The plug-in correlation matrix of a covariance S (``Sampler.get_sigma``, or any symmetric p x p
+    covariance): ``S_ab / sqrt(S_aa S_bb)`` with an exact unit diagonal; NaN in the rows and columns whose
+    diagonal entry is not positive.  The precision side's counterpart is ``partial_correlations(T)``.  Of
+    Sigmaout it is the correlation of the posterior mean covariance, not the posterior mean of the per-sample
+    correlation (``Sampler.get_corr("mean")``), and it carries no uncertainty."""
+    S = np.asarray(S, dtype=np.float64)
+    if S.ndim != 2 or S.shape[0] != S.shape[1]:
+        raise ValueError(f"S must be p x p, got {S.shape}")
+    d = S.diagonal()
+    with np.errstate(divide="ignore", invalid="ignore"):
+        s = np.sqrt(np.where(d > 0, d, np.nan))
+        R = S / (s[:, None] * s[None, :])
+    R[np.diag_indices_from(R)] = np.where(d > 0, 1.0, np.nan)
+    return R
+
+
 def partial_correlation_edges(mean, sd, z=1.96, min_abs=0.0) -> dict:
     """Edges of the graphical model from the posterior mean and standard deviation of the partial
     correlations (``Sampler.get_partial_corr("mean")`` / ``("sd")``, or ``divideconquer(..., return_partial=True)``).
+    It works on any (mean, sd) pair of p x p matrices: given ``Sampler.get_corr("mean")`` / ``("sd")`` (or
+    ``divideconquer(..., return_corr=True)``) it thresholds the marginal correlations, the edges of a
+    co-expression network, the same way.
     Returns ``{"z": |mean| / sd, "edges": bool p x p}``: ``z`` is inf where sd == 0 and mean != 0, and NaN where
     either input is NaN or both are 0; ``edges[a, b]`` holds where ``|mean| >= min_abs`` and ``z-score >= z``
     on the pair (a, b) *and* on (b, a), so it is symmetric; its diagonal is False, and a NaN is no edge."""

@@ -205,7 +205,7 @@ def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hy
                   init_draws=None, iter_draws=None, nranks=1, rank=0, device=0, comm_uid=None,
                   asm_batch=0, return_info=False, device_ingest=True, device_init=True, return_sd=False,
                   n_components=0, rhs=None, probes=None, precision_probes=None, return_precision=False, loglik=False,
-                  predict=None, impute=False, return_partial=False):
+                  predict=None, impute=False, return_partial=False, return_corr=False):
     """Sigmaout = divideconquer(Y,g,k,BURNIN,MCMC,thin,rho)   (divideconquer.m:1).
 
     ``device_ingest`` (default): the zero-column scan and the partition/standardisation
@@ -236,6 +236,16 @@ def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hy
     (``unpermute_partial``: partial correlations do not change with the columns' scaling, so this is a pure
     un-permutation; dropped all-zero columns get NaN, with 1 (mean) and 0 (sd) on the diagonal).
     ``diagnostics.partial_correlation_edges`` turns the pair into the edges of the graphical model.
+
+    ``return_corr``: also accumulate the posterior mean and second moment of the per-sample correlation matrix
+    ``Sigma(s) / sqrt(v v')``, ``v = diag(Sigma(s))``, and of the communalities ``h_a(s) = |Lambda_a(s)|^2 / v_a(s)``
+    on the device (DCFM_FLAG_CORR) and append ``{"mean", "sd", "communality", "communality_sd"}`` after the
+    ``return_partial`` dict (if requested) and before the ``n_components`` dict: the posterior mean (1/effsamp
+    scaling, quirk Q8) and standard deviation of every correlation, p_orig x p_orig, and of every variable's
+    communality, p_orig entries, in the *input's* column order (``unpermute_corr`` / ``unpermute_communality``:
+    correlations and communalities do not change with the columns' scaling, so these are pure un-permutations;
+    dropped all-zero columns get NaN, with 1 (mean) and 0 (sd) on the matrices' diagonal).  The mean is the
+    posterior mean of the correlation, not the plug-in ``diagnostics.correlation(Sigmaout)``.
 
     ``n_components`` > 0: also the leading principal components of Sigmaout, found on the device
     (Sampler.sigma_eigs: ``values``, ``vectors`` p x n_components, ``resid``, ``passes``,
@@ -342,7 +352,8 @@ def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hy
     s0 = rank * gl
     smp = Sampler(n, P, g, K, rho, BURNIN, MCMC, thin, hyper=hyper, seed=seed, nranks=nranks,
                   rank=rank, device=device, inject_draws=iter_draws is not None, asm_batch=asm_batch,
-                  sigma_m2=return_sd, precision_mean=return_precision, partial_corr=return_partial)
+                  sigma_m2=return_sd, precision_mean=return_precision, partial_corr=return_partial,
+                  corr=return_corr)
     try:
         if nranks > 1:
             if comm_uid is None:
@@ -381,6 +392,15 @@ def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hy
             if Rm is not None:                                   # rank 0
                 pcr = {"mean": unpermute_partial(Rm, keep, init.varind, np.asarray(Y).shape[1]),
                        "sd": unpermute_partial(Rs, keep, init.varind, np.asarray(Y).shape[1], diag=0.0)}
+        crr = None
+        if return_corr:
+            Cm, Cs = smp.get_corr("mean"), smp.get_corr("sd")
+            if Cm is not None:                                   # rank 0
+                p0 = np.asarray(Y).shape[1]
+                crr = {"mean": unpermute_corr(Cm, keep, init.varind, p0),
+                       "sd": unpermute_corr(Cs, keep, init.varind, p0, diag=0.0),
+                       "communality": unpermute_communality(smp.get_communality("mean"), keep, init.varind, p0),
+                       "communality_sd": unpermute_communality(smp.get_communality("sd"), keep, init.varind, p0)}
         pcs = smp.sigma_eigs(int(n_components)) if n_components > 0 else None
         sol = None
         if rhs is not None:
@@ -419,6 +439,8 @@ def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hy
         out += (Theta,)
     if return_partial:
         out += (pcr,)
+    if return_corr:
+        out += (crr,)
     if n_components > 0:
         out += (pcs,)
     if rhs is not None:
@@ -551,6 +573,26 @@ def unpermute_partial(R, keep, varind, p_orig, fill=np.nan, diag=1.0):
     dropped = np.setdiff1d(np.arange(p_orig), output_columns(keep, varind))
     out[dropped, dropped] = diag
     return out
+
+
+def unpermute_corr(R, keep, varind, p_orig, fill=np.nan, diag=1.0):
+    """A correlation matrix in Sigmaout's coordinates (``Sampler.get_corr``, or ``diagnostics.correlation`` of a
+    covariance) back in the input's column order.  Correlations are invariant to the columns' scaling --
+    (D S D)_ab / sqrt((D S D)_aa (D S D)_bb) = S_ab / sqrt(S_aa S_bb) for a positive diagonal D -- so this is
+    ``unpermute_partial``'s pure un-permutation: dropped (all-zero, dc:36-39) columns get ``fill`` with ``diag``
+    on their diagonal (1; pass 0 for a matrix of standard deviations)."""
+    return unpermute_partial(R, keep, varind, p_orig, fill=fill, diag=diag)
+
+
+def unpermute_communality(h, keep, varind, p_orig, fill=np.nan):
+    """Per-variable values in Sigmaout's coordinates (``Sampler.get_communality``) back in the input's column
+    order: entry a goes to cols[a] with cols = output_columns(keep, varind).  A communality is a ratio of two
+    variances of the same column, so there is no ``sd``; dropped (all-zero, dc:36-39) columns get ``fill``
+    (NaN: the model says nothing about them)."""
+    h = np.asarray(h, dtype=np.float64)
+    if h.ndim != 1:
+        raise ValueError(f"h must be a vector of p entries, got {h.shape}")
+    return unpermute_vectors(h, keep, varind, p_orig, fill=fill)
 
 
 def unpermute_vectors(V, keep, varind, p_orig, sd=None, fill=0.0):

@@ -41,7 +41,7 @@ class Sampler:
 
     def __init__(self, n, P, g, K, rho, burnin, mcmc, thin, *, hyper: Hyper = Hyper(), seed=0,
                  nranks=1, rank=0, device=0, inject_draws=False, asm_batch=0, flags=0, sigma_m2=False,
-                 precision_mean=False, partial_corr=False):
+                 precision_mean=False, partial_corr=False, corr=False):
         self.lib = _abi.load_library()
         cfg = _abi.DcfmConfig()
         cfg.n, cfg.P, cfg.g, cfg.K = int(n), int(P), int(g), int(K)
@@ -54,7 +54,8 @@ class Sampler:
         cfg.flags = ((_abi.DCFM_FLAG_INJECT_DRAWS if inject_draws else 0) |
                      (_abi.DCFM_FLAG_SIGMA_M2 if sigma_m2 else 0) |
                      (_abi.DCFM_FLAG_PRECISION_MEAN if precision_mean else 0) |
-                     (_abi.DCFM_FLAG_PARTIAL_CORR if partial_corr else 0) | int(flags))
+                     (_abi.DCFM_FLAG_PARTIAL_CORR if partial_corr else 0) |
+                     (_abi.DCFM_FLAG_CORR if corr else 0) | int(flags))
         cfg.asm_batch = int(asm_batch)
         self.cfg = cfg
         h = C.c_void_p()
@@ -297,10 +298,50 @@ class Sampler:
         self._check(self.lib.dcfm_get_partial_corr_cols(self.h, w, int(col0), int(ncols), _ptr(R)))
         return R
 
+    def get_corr(self, which="mean"):
+        """A posterior moment of the correlation matrix (p x p, Fortran order, Sigmaout's coordinates).  Per saved
+        sample ``R(s) = Sigma(s) / sqrt(v v')``, ``v = diag(Sigma(s))``, with a unit diagonal; ``"mean"`` is
+        ``(1/effsamp) sum_s R(s)`` (diagonal exactly saved/effsamp), ``"m2"`` the same sum of ``R(s)**2``, ``"sd"``
+        the posterior standard deviation over the samples saved so far (population form, 0 on the diagonal).
+        The posterior mean of the correlation, not the plug-in ``diagnostics.correlation(get_sigma())``.  Needs
+        ``corr=True``.  Symmetric bit for bit.  Collective like get_sigma(): rank 0 receives it, the others get
+        None."""
+        w = self._moment(which)
+        p = self.P * self.g
+        if self.rank != 0:
+            self._check(self.lib.dcfm_get_corr(self.h, w, None))
+            return None
+        R = np.zeros((p, p), dtype=np.float64, order="F")
+        self._check(self.lib.dcfm_get_corr(self.h, w, _ptr(R)))
+        return R
+
+    def get_corr_cols(self, which, col0: int, ncols: int):
+        """Columns [col0, col0+ncols) of get_corr(which), p x ncols (as get_sigma_cols)."""
+        w = self._moment(which)
+        p = self.P * self.g
+        if self.rank != 0:
+            self._check(self.lib.dcfm_get_corr_cols(self.h, w, int(col0), int(ncols), None))
+            return None
+        R = np.zeros((p, int(ncols)), dtype=np.float64, order="F")
+        self._check(self.lib.dcfm_get_corr_cols(self.h, w, int(col0), int(ncols), _ptr(R)))
+        return R
+
+    def get_communality(self, which="mean"):
+        """A posterior moment of the communalities ``h_a(s) = |Lambda_a(s)|^2 / (|Lambda_a(s)|^2 + omega_a(s))``,
+        the share of each variable's variance that the factors explain (p entries, Sigmaout's coordinates):
+        ``"mean"`` ``(1/effsamp) sum_s h(s)``, ``"m2"`` the same sum of ``h(s)**2``, ``"sd"`` the posterior
+        standard deviation over the samples saved so far (population form).  Needs ``corr=True``.  Not
+        collective: every rank holds all p entries."""
+        w = self._moment(which)
+        hv = np.zeros(self.P * self.g, dtype=np.float64)
+        self._check(self.lib.dcfm_get_communality(self.h, w, _ptr(hv)))
+        return hv
+
     def sigma_block(self) -> dict:
         """This rank's block of Sigmaout: rows [row0, row1) of the lower triangle and its bytes
-        (the mean, plus the second moment with ``sigma_m2``, the precision mean with ``precision_mean`` and the
-        two moments of the partial correlations with ``partial_corr``)."""
+        (the mean, plus the second moment with ``sigma_m2``, the precision mean with ``precision_mean``, the
+        two moments of the partial correlations with ``partial_corr`` and those of the correlations with
+        ``corr``)."""
         out = (C.c_int64 * 3)()
         self._check(self.lib.dcfm_sigma_block(self.h, out))
         return {"row0": int(out[0]), "row1": int(out[1]), "bytes": int(out[2])}

@@ -83,6 +83,13 @@ extern "C" {
                                         kernels of partial_corr.hip per flush), for
                                         dcfm_get_partial_corr[_cols]; off: nothing is allocated or
                                         launched                                          */
+#define DCFM_FLAG_CORR         0x400u  /* also accumulate the posterior mean and second moment of the
+                                        per-sample correlation matrix D(s)^-1/2 Sigma(s) D(s)^-1/2 and of
+                                        the communalities (two more buffers the size of this rank's
+                                        Sigmaout block, the per-sample omega slots, a p x asm_batch scale
+                                        array, two p-vectors and the two kernels of corr.hip per flush),
+                                        for dcfm_get_corr[_cols] and dcfm_get_communality; off: nothing
+                                        is allocated or launched                           */
 
 typedef struct dcfm_handle dcfm_handle;
 
@@ -214,7 +221,8 @@ int  dcfm_get_sigma_cols(dcfm_handle *h, int64_t col0, int64_t ncols, double *ou
  * the ranks), out[2] = its device bytes for Sigmaout (~p^2 / (2 nranks) * 8; once more
  * with DCFM_FLAG_SIGMA_M2, the second moment beside the mean, and once more with
  * DCFM_FLAG_PRECISION_MEAN, the precision accumulator, and twice more with
- * DCFM_FLAG_PARTIAL_CORR, the two moments of the partial correlations). */
+ * DCFM_FLAG_PARTIAL_CORR, the two moments of the partial correlations, and twice more with
+ * DCFM_FLAG_CORR, the two moments of the correlations). */
 int  dcfm_sigma_block(const dcfm_handle *h, int64_t out[3]);
 int64_t dcfm_saved_samples(const dcfm_handle *h);
 /* Posterior moments of Sigma's entries.  With Sigma(s) the matrix dc:182-192 builds from saved
@@ -268,6 +276,31 @@ int  dcfm_get_precision_mean(dcfm_handle *h, double *out);
  * symmetric bit for bit; layout, striping and collective semantics as dcfm_get_sigma_moment[_cols]. */
 int  dcfm_get_partial_corr_cols(dcfm_handle *h, int32_t which, int64_t col0, int64_t ncols, double *out);
 int  dcfm_get_partial_corr(dcfm_handle *h, int32_t which, double *out);
+/* Posterior moments of the (marginal) correlation matrix and of the communalities (DCFM_FLAG_CORR at
+ * dcfm_create, else DCFM_ERR_INVALID).  The columns are standardised before the sweep (dc:57-59), but the
+ * diagonal of Sigma(s) is not 1: v_a(s) = Sigma(s)_aa = |Lambda_a(s)|^2 + omega_a(s) moves from sample to
+ * sample.  Per saved sample s, with c_ab = 1 for a, b in one shard and rho across (dc:186-189),
+ *   R(s)_ab = c_ab Lambda_a(s) . Lambda_b(s) / sqrt(v_a(s) v_b(s))  (a != b),   R(s)_aa = 1 exactly,
+ *   h_a(s)  = |Lambda_a(s)|^2 / v_a(s)          the communality: the share of variable a's variance that the
+ *                                               factors explain (invariant to a rotation of the factors),
+ * and `which` selects, for dcfm_get_corr[_cols] (p x p) and dcfm_get_communality (p doubles) alike,
+ *   DCFM_SIGMA_MEAN  (1/effsamp) sum_s R(s) resp. h(s), with the same effsamp = mcmc/thin scaling (quirk Q8)
+ *                    as Sigmaout: the diagonal of the matrix is exactly saved / effsamp;
+ *   DCFM_SIGMA_M2    (1/effsamp) sum_s R(s).^2 resp. h(s).^2, the same scaling;
+ *   DCFM_SIGMA_SD    sqrt(max(0, r M2 - (r MEAN).^2)), r = effsamp / dcfm_saved_samples(h): the posterior
+ *                    standard deviation (population form) over the samples saved so far; 0 on the diagonal.
+ * The mean is the posterior mean of the per-sample correlation, not the plug-in D^-1/2 Sigmaout D^-1/2, and it
+ * comes with an SD.  All zeros before the first saved sample; SD with no saved sample and a `which` outside
+ * the three are DCFM_ERR_INVALID.  No inversion is involved and |R(s)_ab| <= 1: an entry of R(s) is accurate
+ * to about (2 K + 8) eps whatever the conditioning of Sigma(s); a non-finite or non-positive v_a(s) gives NaN,
+ * which runs through.  M2 - mean^2 cancels: an entry's variance keeps about eps M2 / var relative accuracy.
+ * Device bytes: twice this rank's Sigmaout block (dcfm_sigma_block), plus p (asm_batch + 2) doubles and the
+ * omega slots 2 p asm_batch.  The matrix is in Sigmaout's coordinates, symmetric bit for bit; layout, striping
+ * and collective semantics as dcfm_get_sigma_moment[_cols].  dcfm_get_communality is not collective: every
+ * rank holds all p entries (bitwise equal on all ranks) and `out` must not be NULL on any rank. */
+int  dcfm_get_corr_cols(dcfm_handle *h, int32_t which, int64_t col0, int64_t ncols, double *out);
+int  dcfm_get_corr(dcfm_handle *h, int32_t which, double *out);
+int  dcfm_get_communality(dcfm_handle *h, int32_t which, double *out);
 /* Error of Sigmaout against a truth Sigma0 = U U' + diag(s) given in the same permuted,
  * standardised coordinates (U: p x r column-major, r <= 32; s: p), computed on the
  * device (Sigmaout never leaves HBM; c5: 80 GB).  out[0] = ||Sigmaout - Sigma0||_F,

@@ -7,7 +7,7 @@
  * on the GPU).  Commands:
  *   h = dcfm_mex('create', cfg)           cfg fields n P g K rho burnin mcmc thin as bs df ad1
  *                                         bd1 ad2 bd2 seed device inject asm_batch sigma_m2
- *                                         precision_mean partial_corr
+ *                                         precision_mean partial_corr corr
  *   dcfm_mex('set_data', h, Yd)           Yd n x P x g (dc:49-59 done by the caller)
  *   dcfm_mex('set_data_raw', h, Y0, cols) raw n x p0 data + int64 0-based columns (dc:48-59 on GPU)
  *   dcfm_mex('set_state', h, Lambda, ps, omega, psijh, Plam, X, Z, delta, tauh)
@@ -30,6 +30,12 @@
  *                                         -T_ab / sqrt(T_aa * T_bb), T = inv(Sigma_s), over the saved samples
  *                                         (needs cfg.partial_corr = 1), p x p or the columns col0 ..
  *                                         col0+ncols-1 (0-based), p x ncols; Sigmaout's coordinates
+ *   R = dcfm_mex('corr', h, which[, col0, ncols])   which = 'mean' | 'm2' | 'sd': posterior mean, second moment
+ *                                         or standard deviation of the correlations S_ab / sqrt(S_aa * S_bb),
+ *                                         S = Sigma_s, over the saved samples (needs cfg.corr = 1), p x p or the
+ *                                         columns col0 .. col0+ncols-1 (0-based), p x ncols; Sigmaout's coordinates
+ *   c = dcfm_mex('communality', h, which) the same three moments of the communalities
+ *                                         sum(Lambda_s(a,:).^2) / S_aa (needs cfg.corr = 1), p x 1
  *   Y = dcfm_mex('sigma_apply', h, V)     Y = Sigmaout * V on the device, V p x nv (any nv >= 1), in
  *                                         Sigmaout's permuted, standardised coordinates
  *   [d, V, res] = dcfm_mex('sigma_eigs', h, r[, tol, max_passes, seed])   the r <= 32 largest eigenpairs
@@ -161,6 +167,7 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         if (fld(s, "sigma_m2", 0) != 0) c.flags |= DCFM_FLAG_SIGMA_M2;
         if (fld(s, "precision_mean", 0) != 0) c.flags |= DCFM_FLAG_PRECISION_MEAN;
         if (fld(s, "partial_corr", 0) != 0) c.flags |= DCFM_FLAG_PARTIAL_CORR;
+        if (fld(s, "corr", 0) != 0) c.flags |= DCFM_FLAG_CORR;
         c.asm_batch = (int32_t)fld(s, "asm_batch", 0);
         int i = 0;
         while (i < NSLOT && S[i].h) ++i;
@@ -299,8 +306,12 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
                               (long long)p);
         plhs[0] = mxCreateDoubleMatrix((mwSize)p, (mwSize)p, mxREAL);
         ck(t->h, dcfm_get_sigma(t->h, mxGetDoubles(plhs[0])));
-    } else if (!strcmp(cmd, "sigma_moment") || !strcmp(cmd, "partial_corr")) {
-        /* M = dcfm_mex('sigma_moment', h, which[, col0, ncols]), R = dcfm_mex('partial_corr', h, which[, col0, ncols]) */
+    } else if (!strcmp(cmd, "sigma_moment") || !strcmp(cmd, "partial_corr") || !strcmp(cmd, "corr") ||
+               !strcmp(cmd, "communality")) {
+        /* M = dcfm_mex('sigma_moment', h, which[, col0, ncols]), R = dcfm_mex('partial_corr' | 'corr', h, which[, col0,
+         * ncols]), c = dcfm_mex('communality', h, which) */
+        const int vec = !strcmp(cmd, "communality");   /* a p-vector: no column range */
+        if (vec && nrhs != 3) mexErrMsgIdAndTxt("dcfm:nargs", "'%s' takes 2 arguments, got %d", cmd, nrhs - 1);
         if (nrhs != 3 && nrhs != 5)
             mexErrMsgIdAndTxt("dcfm:nargs", "'%s' takes 2 or 4 arguments, got %d", cmd, nrhs - 1);
         /* the arguments that need no handle first: a malformed call never reaches the library */
@@ -321,11 +332,15 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         }
         slot *t = get(prhs[1]);
         const int64_t p = t->P * t->g;               /* the size the library writes */
-        if (nc < 0) nc = (double)p;
-        if (c0 + nc > (double)p)
+        if (nc < 0) nc = vec ? 1.0 : (double)p;
+        if (!vec && c0 + nc > (double)p)
             mexErrMsgIdAndTxt("dcfm:arg", "columns [%g, %g) outside 0..p = %lld", c0, c0 + nc, (long long)p);
         plhs[0] = mxCreateDoubleMatrix((mwSize)p, (mwSize)nc, mxREAL);
-        if (!strcmp(cmd, "partial_corr"))
+        if (vec)
+            ck(t->h, dcfm_get_communality(t->h, which, mxGetDoubles(plhs[0])));
+        else if (!strcmp(cmd, "corr"))
+            ck(t->h, dcfm_get_corr_cols(t->h, which, (int64_t)c0, (int64_t)nc, mxGetDoubles(plhs[0])));
+        else if (!strcmp(cmd, "partial_corr"))
             ck(t->h, dcfm_get_partial_corr_cols(t->h, which, (int64_t)c0, (int64_t)nc, mxGetDoubles(plhs[0])));
         else
             ck(t->h, dcfm_get_sigma_moment_cols(t->h, which, (int64_t)c0, (int64_t)nc, mxGetDoubles(plhs[0])));

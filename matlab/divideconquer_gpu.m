@@ -1,4 +1,4 @@
-function [Sigmaout, Sigmasd, Q, logdet] = divideconquer_gpu(Y, g, k, BURNIN, MCMC, thin, rho, seed, Vprec)
+function [Sigmaout, Sigmasd, Q, logdet, Corr] = divideconquer_gpu(Y, g, k, BURNIN, MCMC, thin, rho, seed, Vprec)
 % DIVIDECONQUER_GPU  Sigmaout = divideconquer_gpu(Y,g,k,BURNIN,MCMC,thin,rho[,seed])
 % Same arguments and output as divideconquer.m:1 (posterior-mean covariance in the
 % permuted, standardised coordinates, quirk Q7), with the driver (dc:29-87) and the loop
@@ -14,6 +14,10 @@ function [Sigmaout, Sigmasd, Q, logdet] = divideconquer_gpu(Y, g, k, BURNIN, MCM
 % [Sigmaout, Sigmasd, Q, logdet] = divideconquer_gpu(..., seed, Vprec) with Vprec p0 x nv (nv <= 32, one row
 % per column of Y) also records Q(:,:,s) = V' * inv(Sigma_s) * V and logdet(s) = log(det(Sigma_s)) at every saved
 % sample (set_precision_probes), V = Vprec(keepcols(varind), :) the block in Sigmaout's coordinates.
+% [Sigmaout, Sigmasd, Q, logdet, Corr] = divideconquer_gpu(...) also returns the struct Corr with the posterior
+% mean and standard deviation of the per-sample correlation matrix Sigma_s ./ sqrt(diag(Sigma_s) * diag(Sigma_s)')
+% (Corr.mean, Corr.sd; Sigmaout's coordinates) and of the communalities (Corr.communality, Corr.communality_sd;
+% p x 1), accumulated on the GPU beside Sigmaout (cfg.corr).
 if nargin < 8 || isempty(seed), seed = 0; end
 if nargin < 9, Vprec = []; end
 [n, p0] = size(Y);
@@ -26,7 +30,7 @@ end
 varind = randperm(p);                                      % dc:50
 cfg = struct('n', n, 'P', P, 'g', g, 'K', K, 'rho', rho, 'burnin', BURNIN, 'mcmc', MCMC, ...
              'thin', thin, 'as', 1, 'bs', 0.3, 'df', 3, 'ad1', 2, 'bd1', 1, 'ad2', 2, 'bd2', 1, ...
-             'seed', seed, 'sigma_m2', double(nargout > 1));
+             'seed', seed, 'sigma_m2', double(nargout > 1), 'corr', double(nargout > 4));
 h = dcfm_mex('create', cfg);
 cleanup = onCleanup(@() dcfm_mex('destroy', h));
 dcfm_mex('set_data_raw', h, Y, int64(keepcols(varind) - 1));  % dc:48-59 on the device
@@ -36,4 +40,9 @@ dcfm_mex('run', h, 1, BURNIN + MCMC);                          % dc:90-197
 Sigmaout = dcfm_mex('get_sigma', h, p);
 if nargout > 1, Sigmasd = dcfm_mex('sigma_moment', h, 'sd'); end
 if nargout > 2, [Q, logdet] = dcfm_mex('precision_draws', h); end
+if nargout > 4
+    Corr = struct('mean', dcfm_mex('corr', h, 'mean'), 'sd', dcfm_mex('corr', h, 'sd'), ...
+                  'communality', dcfm_mex('communality', h, 'mean'), ...
+                  'communality_sd', dcfm_mex('communality', h, 'sd'));
+end
 end

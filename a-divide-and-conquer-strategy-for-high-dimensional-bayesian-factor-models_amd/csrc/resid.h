@@ -50,8 +50,10 @@ __device__ __forceinline__ void ps_omega_store(const Dims &d, double SS, double 
 //      Beyond kappa_max (or SS_j <= 0) the row takes dc:169's residual instead: K <= 32 the wave's 8 rows
 //      in the same launch (resid_rows8), K > 32 the row's 32-row tile in k_resid_flagged.
 //      sqrt(yy_j) as v * rsq(v) from the hardware estimate (a bound needs no correct rounding; the factor
-//      1.01 covers its error); a zero yy_j gives NaN, read as "take the residual".
-//      kappa_max = 0 rejects every row (DCFM_FLAG_GUARD_ALL), infinity none with SS_j > 0.
+//      1.01 covers its error).  A zero yy_j makes that product NaN, and fmax returns its other argument:
+//      the a-priori bound would drop out unseen, so the accepting conjunction asks for yy_j > 0 itself (a
+//      zero, negative or NaN yy_j takes the residual; preprocessing drops zero columns, so no sweep pays).
+//      kappa_max = 0 rejects every row (DCFM_FLAG_GUARD_ALL), infinity none with SS_j > 0 and yy_j > 0.
 #ifndef DCFM_KAPPA_MAX
 #define DCFM_KAPPA_MAX 1e3
 #endif
@@ -59,7 +61,7 @@ constexpr double KAPPA_IDENTITY_MAX = DCFM_KAPPA_MAX;
 __device__ __forceinline__ bool ss_identity_reject(double yy, double SS, double mag, double sabs, double kappa_max) {
     const double rt = 1.01 * (yy * __builtin_amdgcn_rsq(yy) + sabs);
     const double num = fmax(rt * rt, 1.01 * (yy + mag));
-    return !(SS > 0.0 && num <= kappa_max * SS);
+    return !(SS > 0.0 && yy > 0.0 && num <= kappa_max * SS);
 }
 
 // ---- dc:169 as written, fp64 MFMA v_mfma_f64_16x16x4.  One chunk = rows i0 .. i0+15 of i against NH tiles

@@ -55,9 +55,24 @@ __global__ __launch_bounds__(256) void k_save(Dims d, const double *__restrict__
 // (batch x K) runs in chunks of 16 through double-buffered LDS, stored k-major
 // with a 144-double pitch: an MFMA operand read (16 consecutive rows x 4 k) is a
 // conflict-free ds_read_b64, and the next chunk's global loads are in flight
-// during the current chunk's 64 MFMAs per wave.  One barrier per chunk.
+// during the current chunk's 64 MFMAs per wave.  One barrier per chunk, in front of the
+// chunk's last k-step: the operand reads run one k-step ahead of the MFMAs across the
+// chunks, the next chunk is staged in the middle of the MFMA stream, and the panel loads
+// carry no exec-mask branch into it (r08: driver flush 1,084 -> 942 us, 96-sample flush
+// 18.80 -> 17.05 ms, Sigma bitwise unchanged).
 // ============================================================================
 constexpr int AKC = ASM_KC, ALD = ASM_TILE + 16, ASM_THREADS = 256;
+// A/B switches of the chunk loop (tools/build_variant.sh; profiles/r06_ab_summary.txt, r08)
+#ifndef DCFM_ASM_PIPE
+#define DCFM_ASM_PIPE 1        // 0: the A/B baseline, one loop with a break for the partial last chunk
+#endif
+#ifndef DCFM_ASM_GLB
+#define DCFM_ASM_GLB 1         // 0: the A/B baseline, the panel loads of rows past p predicated (a branch per load)
+#endif
+constexpr bool ASM_GLB = DCFM_ASM_GLB;
+#ifndef DCFM_ASM_LSTORE_AT
+#define DCFM_ASM_LSTORE_AT 2   // the next chunk's LDS stores follow this k-step of the chunk (1 .. 3)
+#endif
 
 __device__ __forceinline__ void assemble_tile(const Dims &d, const double *__restrict__ Lb, int LDB, int kext,
                                               const double *__restrict__ wsum, double inv_eff, int2 T, int T0,
@@ -81,21 +96,28 @@ __device__ __forceinline__ void assemble_tile(const Dims &d, const double *__res
     const double *pb = Lb + (size_t)(vb ? gb : 0) * LDB + 8 * shalf;
     const d2 zero2 = {0.0, 0.0};
     d2 ra[4], rb[4];
+    // rows past p: the loads go to row 0 (pa, pb) without a branch and the staging writes zeros (a load under
+    // `va ? ... : 0` compiles to an exec-mask branch per load: eight in every chunk's MFMA stream)
     auto gload = [&](int kc) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            ra[i] = va ? *reinterpret_cast<const d2 *>(pa + kc + 2 * i) : zero2;
-            rb[i] = vb ? *reinterpret_cast<const d2 *>(pb + kc + 2 * i) : zero2;
+            if (ASM_GLB) {
+                ra[i] = *reinterpret_cast<const d2 *>(pa + kc + 2 * i);
+                rb[i] = *reinterpret_cast<const d2 *>(pb + kc + 2 * i);
+            } else {
+                ra[i] = va ? *reinterpret_cast<const d2 *>(pa + kc + 2 * i) : zero2;
+                rb[i] = vb ? *reinterpret_cast<const d2 *>(pb + kc + 2 * i) : zero2;
+            }
         }
     };
     auto lstore = [&](int buf) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int k = 8 * shalf + 2 * i;
-            As[buf][k][srow] = sA * ra[i].x;
-            As[buf][k + 1][srow] = sA * ra[i].y;
-            Bs[buf][k][srow] = rb[i].x;
-            Bs[buf][k + 1][srow] = rb[i].y;
+            As[buf][k][srow] = ASM_GLB && !va ? 0.0 : sA * ra[i].x;
+            As[buf][k + 1][srow] = ASM_GLB && !va ? 0.0 : sA * ra[i].y;
+            Bs[buf][k][srow] = ASM_GLB && !vb ? 0.0 : rb[i].x;
+            Bs[buf][k + 1][srow] = ASM_GLB && !vb ? 0.0 : rb[i].y;
         }
     };
     gload(0);      // ahead of the tile's Sigma loads: staging chunk 0 waits only for its panels
@@ -121,6 +143,66 @@ __device__ __forceinline__ void assemble_tile(const Dims &d, const double *__res
     }
     lstore(0);
     __syncthreads();
+    // one k-step: the wave's operands of k = 4 s4 .. + 3 from LDS, and its 16 MFMAs
+    auto opload = [&](int buf, int s4, double (&a)[4], double (&b)[4]) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) a[u] = As[buf][4 * s4 + q][wa + 16 * u + r];
+#pragma unroll
+        for (int v = 0; v < 4; ++v) b[v] = Bs[buf][4 * s4 + q][wb + 16 * v + r];
+    };
+    auto mma = [&](const double (&a)[4], const double (&b)[4]) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int v = 0; v < 4; ++v) acc[u][v] = mfma16x16x4(a[u], b[v], acc[u][v]);
+    };
+#if DCFM_ASM_PIPE
+    // Whole chunks run in a loop of NS k-steps without a branch between them; the last chunk (1 .. NS
+    // k-steps) follows it.  The operand reads run one k-step ahead of the MFMAs, across the chunks: a
+    // chunk's barrier stands in front of its LAST k-step's MFMAs, whose operands are in registers by then,
+    // and the next chunk's first operands are read right behind it, under those 16 MFMAs.  The next chunk's
+    // panels (loaded at the chunk's head) are staged after k-step LAT, one k-step ahead of the barrier, so
+    // their LDS stores are not what the barrier's arrival waits for.  Every accumulator takes the same
+    // products in the same k order as the plain loop.
+    constexpr int NS = AKC / 4, LAT = DCFM_ASM_LSTORE_AT;
+    static_assert(1 <= LAT && LAT < NS, "the staging precedes the chunk's barrier");
+    const int nch = (kext + AKC - 1) / AKC;             // chunks; all but the last are whole
+    const int nlast = (kext - (nch - 1) * AKC) / 4;     // k-steps of the last one, 1 .. NS (kext is a multiple of 4)
+    double a[2][4], b[2][4];
+    int buf = 0;
+    opload(0, 0, a[0], b[0]);
+    for (int c = 0; c < nch - 1; ++c, buf ^= 1) {
+        gload((c + 1) * AKC);
+#pragma unroll
+        for (int s4 = 0; s4 < NS; ++s4) {
+            if (s4 + 1 < NS) {
+                opload(buf, s4 + 1, a[(s4 + 1) & 1], b[(s4 + 1) & 1]);
+            } else {
+                __builtin_amdgcn_sched_barrier(0);
+                __syncthreads();
+                opload(buf ^ 1, 0, a[0], b[0]);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            mma(a[s4 & 1], b[s4 & 1]);
+            if (s4 + 1 == LAT) {
+                // the wait for the panels belongs HERE: neither the scheduler nor the optimiser may lift the
+                // staging's row scaling, and with it the wait, to the head of the chunk
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) asm volatile("" : "+v"(ra[i]), "+v"(rb[i]));
+                lstore(buf ^ 1);
+            }
+        }
+    }
+    // the last chunk (block-uniform count); its first operands are in a[0], b[0]
+    mma(a[0], b[0]);
+#pragma unroll
+    for (int s4 = 1; s4 < NS; ++s4) {
+        if (s4 >= nlast) break;
+        opload(buf, s4, a[1], b[1]);
+        mma(a[1], b[1]);
+    }
+#else
     for (int kc = 0, buf = 0; kc < kext; kc += AKC, buf ^= 1) {
         const bool more = kc + AKC < kext;
         if (more) gload(kc + AKC);
@@ -129,18 +211,13 @@ __device__ __forceinline__ void assemble_tile(const Dims &d, const double *__res
         for (int s4 = 0; s4 < AKC / 4; ++s4) {
             if (4 * s4 >= nk4) break;            // block-uniform: the last chunk may be partial
             double a[4], b[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) a[u] = As[buf][4 * s4 + q][wa + 16 * u + r];
-#pragma unroll
-            for (int v = 0; v < 4; ++v) b[v] = Bs[buf][4 * s4 + q][wb + 16 * v + r];
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-#pragma unroll
-                for (int v = 0; v < 4; ++v) acc[u][v] = mfma16x16x4(a[u], b[v], acc[u][v]);
+            opload(buf, s4, a, b);
+            mma(a, b);
         }
         if (more) lstore(buf ^ 1);
         __syncthreads();
     }
+#endif
     if (cross) {   // acc = old + (rho / effsamp) L_a L_b': plain stores (the whole tile is below the diagonal)
 #pragma unroll
         for (int u = 0; u < 4; ++u)

@@ -12,9 +12,10 @@ Import through the repo-root helper (the directory name has hyphens)::
 from ._abi import DcfmError, load_library, EXPORTS, LIB_PATH
 from .sampler import Hyper, Sampler, rng_fill, count_nonzero_columns, STATE_FIELDS
 from . import diagnostics
-from .diagnostics import heldout_log_density, summarize_probes, partial_correlations, partial_correlation_edges, correlation, waic, conditional_log_density
+from .diagnostics import heldout_log_density, summarize_probes, partial_correlations, partial_correlation_edges, correlation, waic, conditional_log_density, regression_summary
 from .driver import divideconquer, preprocess, preprocess_device, shard_columns, partition_standardize, initial_state, local_state, truth_factors, output_columns, unpermute_sigma, unpermute_vectors, permute_vectors, unpermute_precision, unpermute_partial, unpermute_corr, unpermute_communality
 from .driver import preprocess_missing, partition_standardize_missing, observed_moments, unstandardize_imputation
+from .driver import column_moments, unstandardize_prediction, unstandardize_regression
 
 __all__ = [
     "preprocess_missing", "partition_standardize_missing", "observed_moments", "unstandardize_imputation",
@@ -25,4 +26,5 @@ __all__ = [
     "summarize_probes",
     "heldout_log_density", "unpermute_precision", "partial_correlations", "unpermute_partial", "partial_correlation_edges",
     "correlation", "unpermute_corr", "unpermute_communality", "waic", "conditional_log_density",
+    "regression_summary", "column_moments", "unstandardize_prediction", "unstandardize_regression",
 ]

@@ -31,6 +31,7 @@ DCFM_FLAG_SIGMA_M2 = 0x80        # accumulate the second moment of the per-sampl
 DCFM_FLAG_PRECISION_MEAN = 0x100  # accumulate the posterior mean of the per-sample Sigma^-1 (get_precision_mean)
 DCFM_FLAG_PARTIAL_CORR = 0x200    # accumulate the mean and second moment of the per-sample partial correlations
 DCFM_FLAG_CORR = 0x400            # accumulate the mean and second moment of the per-sample correlations and communalities
+DCFM_FLAG_REGRESSION = 0x800      # allow set_regression: the factor panels of the per-sample Sigma^-1 at every flush
 # `which` of dcfm_get_sigma_moment[_cols], dcfm_get_partial_corr[_cols], dcfm_get_corr[_cols], dcfm_get_communality
 DCFM_SIGMA_MEAN = 0
 DCFM_SIGMA_M2 = 1
@@ -59,7 +60,7 @@ EXPORTS = (
     "dcfm_get_partial_corr_cols", "dcfm_get_partial_corr",
     "dcfm_get_corr_cols", "dcfm_get_corr", "dcfm_get_communality",
     "dcfm_set_loglik", "dcfm_get_loglik", "dcfm_set_predict", "dcfm_get_predict",
-    "dcfm_set_missing", "dcfm_get_imputed",
+    "dcfm_set_missing", "dcfm_get_imputed", "dcfm_set_regression", "dcfm_get_regression",
 )
 
 
@@ -150,6 +151,8 @@ def load_library(path: Path | None = None):
         "dcfm_get_loglik": (C.c_int, [vp, _DP, _DP, C.POINTER(C.c_int64)]),
         "dcfm_set_predict": (C.c_int, [vp, _DP, C.POINTER(C.c_uint8), C.c_int32, C.c_int64]),
         "dcfm_get_predict": (C.c_int, [vp, _DP, _DP, _DP, _DP, _DP, C.POINTER(C.c_int64)]),
+        "dcfm_set_regression": (C.c_int, [vp, C.POINTER(C.c_int64), C.c_int32]),
+        "dcfm_get_regression": (C.c_int, [vp, _DP, _DP, _DP, _DP, _DP, _DP, C.POINTER(C.c_int64)]),
         "dcfm_set_missing": (C.c_int, [vp, C.POINTER(C.c_uint8), C.c_int64]),
         "dcfm_get_imputed": (C.c_int, [vp, _DP, _DP, _DP, C.POINTER(C.c_int64)]),
         "dcfm_set_profiling": (C.c_int, [vp, C.c_int]),

@@ -249,7 +249,8 @@ static int alloc_buffers(dcfm_handle *h) {
         TRY(dalloc(h, &h->pc.PC, (size_t)(tri(b.T1) - tri(b.T0)) * ASM_TILE * ASM_TILE));
         TRY(dalloc(h, &h->pc.PC2, (size_t)(tri(b.T1) - tri(b.T0)) * ASM_TILE * ASM_TILE));
     }
-    if (c.flags & (DCFM_FLAG_PRECISION_MEAN | DCFM_FLAG_PARTIAL_CORR)) {   // their factor panels and K x K scratch
+    // their factor panels and K x K scratch; DCFM_FLAG_REGRESSION reads the same panels (regression.hip)
+    if (c.flags & (DCFM_FLAG_PRECISION_MEAN | DCFM_FLAG_PARTIAL_CORR | DCFM_FLAG_REGRESSION)) {
         PrecMean &pm = h->pm;
         pm.KH = round_up(h->B * d.K, ASM_KC);
         TRY(dalloc(h, &pm.pfac, p * 4 * (size_t)pm.KH));
@@ -264,7 +265,8 @@ static int alloc_buffers(dcfm_handle *h) {
         TRY(dalloc(h, &cr.H, p));
         TRY(dalloc(h, &cr.H2, p));
     }
-    if (c.flags & (DCFM_FLAG_SIGMA_M2 | DCFM_FLAG_PRECISION_MEAN | DCFM_FLAG_PARTIAL_CORR | DCFM_FLAG_CORR)) {   // each saved sample's own omega
+    if (c.flags & (DCFM_FLAG_SIGMA_M2 | DCFM_FLAG_PRECISION_MEAN | DCFM_FLAG_PARTIAL_CORR | DCFM_FLAG_CORR |
+                   DCFM_FLAG_REGRESSION)) {   // each saved sample's own omega
         TRY(dalloc(h, &b.wslot[0], p * (size_t)h->B));
         TRY(dalloc(h, &b.wslot[1], p * (size_t)h->B));
     }
@@ -380,6 +382,7 @@ void dcfm_destroy(dcfm_handle *h) {
     if (h->ll_mem) (void)hipFree(h->ll_mem);
     if (h->pred_mem) (void)hipFree(h->pred_mem);
     if (h->imp_mem) (void)hipFree(h->imp_mem);
+    if (h->reg_mem) (void)hipFree(h->reg_mem);
     if (h->sasm && h->sasm != h->stream) (void)hipStreamDestroy(h->sasm);
     if (h->side && h->side != h->stream) (void)hipStreamDestroy(h->side);
     if (h->sdraw && h->sdraw != h->stream) (void)hipStreamDestroy(h->sdraw);
@@ -423,10 +426,15 @@ static int flush_batch(dcfm_handle *h) {
         launch_assemble(d, b, b.Lb[lb], b.wsum[lb], kext, 1.0 / effsamp, h->sasm);
         // DCFM_FLAG_SIGMA_M2: the batch's samples one by one into the second moment
         if (b.Sigma2) launch_assemble_m2(d, b, b.Lb[lb], b.wslot[lb], h->batch, h->B, 1.0 / effsamp, h->sasm);
-        // the factor panels of the batch's per-sample inverses, once for both of their readers
-        if (h->pm.pfac) launch_precision_panels(d, b, h->pm, b.Lb[lb], b.wslot[lb], h->batch, h->B, h->sasm);
+        // the factor panels of the batch's per-sample inverses, once for all of their readers
+        if (h->pm.pfac && (h->pm.Prec || h->pc.PC || h->rg.q)) launch_precision_panels(d, b, h->pm, b.Lb[lb], b.wslot[lb], h->batch, h->B, h->sasm);
         // DCFM_FLAG_PRECISION_MEAN: the inverses into the precision mean
         if (h->pm.Prec) launch_precision_mean(d, b, h->pm, b.wslot[lb], h->batch, h->B, 1.0 / effsamp, h->sasm);
+        // dcfm_set_regression: the coefficients of the batch's samples, from the panels as the panel stage left them
+        if (h->rg.q) {
+            launch_regression(d, b, h->pm, h->rg, b.Lb[lb], b.wslot[lb], h->batch, h->B, h->sasm);
+            h->reg_n += h->batch;
+        }
         // DCFM_FLAG_PARTIAL_CORR: the panels scaled in place, the partial correlations into their two moments
         if (h->pc.PC) launch_partial_corr(d, b, h->pm, h->pc, b.wslot[lb], h->batch, h->B, 1.0 / effsamp, h->sasm);
         // DCFM_FLAG_CORR: the rows' scales and communalities, the per-sample correlations into their two moments

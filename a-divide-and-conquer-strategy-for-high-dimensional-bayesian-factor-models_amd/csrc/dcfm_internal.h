@@ -23,9 +23,9 @@
 //   sloc   [G][KW], sall [g][KW]  column sums (all-gathered)
 //   Lb     [2][p][LDB]   saved Lambda rows of an assembly batch (double-buffered), sample s at cols s*K..
 //   wsum   [2][p]        sum of saved omega of the batch
-//   wslot  [2][p][B]     DCFM_FLAG_SIGMA_M2 / _PRECISION_MEAN / _PARTIAL_CORR / _CORR: each saved sample's own omega (slot s of row a at a*B + s)
+//   wslot  [2][p][B]     DCFM_FLAG_SIGMA_M2 / _PRECISION_MEAN / _PARTIAL_CORR / _CORR / _REGRESSION: each saved sample's own omega (slot s of row a at a*B + s)
 //   Prec   [ntiles][128][128]  DCFM_FLAG_PRECISION_MEAN: mean of the per-sample Sigma^{-1}, laid out as Sigma
-//   pfac   [p][4 KH]     DCFM_FLAG_PRECISION_MEAN / _PARTIAL_CORR: the factor panels of a flush (precision_mean.hip), KH = round_up(B K, 16);
+//   pfac   [p][4 KH]     DCFM_FLAG_PRECISION_MEAN / _PARTIAL_CORR / _REGRESSION: the factor panels of a flush (precision_mean.hip), KH = round_up(B K, 16);
 //                        pscr [(2 g + 1) B][K][K] the shards' H_m, B_m^{-1} and the slots' S^{-1}
 //   PC, PC2 [ntiles][128][128]  DCFM_FLAG_PARTIAL_CORR: mean and second moment of the per-sample partial
 //                        correlations, laid out as Sigma (partial_corr.hip; it shares pfac, pscr, wslot)
@@ -236,7 +236,8 @@ struct Impute {
 // Precision mean (precision_mean.hip, DCFM_FLAG_PRECISION_MEAN; all null when off).  Kept out of Bufs, which
 // the sweep's kernels take by value: Prec the accumulator (laid out as Bufs::Sigma), pfac the factor panels of
 // a flush, pscr the K x K scratch, KH the columns of a quarter of pfac (B K rounded up to ASM_KC).
-// DCFM_FLAG_PARTIAL_CORR alone allocates pfac and pscr (the panel stage is shared) and leaves Prec null
+// DCFM_FLAG_PARTIAL_CORR or DCFM_FLAG_REGRESSION alone allocates pfac and pscr (the panel stage is shared) and
+// leaves Prec null
 struct PrecMean {
     double *Prec, *pfac, *pscr;
     int KH;
@@ -251,6 +252,20 @@ struct PartialCorr {
 // H, H2 [p] the two moments of the communalities (all p rows on every rank)
 struct Corr {
     double *C, *C2, *cscale, *H, *H2;
+};
+// Regression coefficients (regression.hip, DCFM_FLAG_REGRESSION with dcfm_set_regression; q == 0 when off), passed
+// to its kernels by value.  resp [q] the response rows; the nsh distinct shards that hold one are numbered
+// ascending: tof [g] a shard's number or -1, grp [q] the responses' positions in R grouped by shard number (R's
+// order inside a group), goff [nsh + 1] the groups' starts.  scr [B][sstride] the slots' scratch: [C (q q) | R2 (q)]
+// and, wofs doubles in, [W_G | W_A[0] .. W_A[nsh - 1]], each K4 x qp row-major (K4 = K rounded up to 4, qp = q to
+// 16; the padding stays the zero it was allocated as).  The accumulators: sB, sB2 [p][q] row-major, sC, sC2
+// [q q + q] = the sums of [C | R2] and of their squares
+struct Regress {
+    int q, qp, nsh, K4;
+    const int *resp, *grp, *goff, *tof;
+    double *scr;
+    size_t sstride, wofs;
+    double *sB, *sB2, *sC, *sC2;
 };
 // Bufs::sync: [0] the X operators (k_xdraw, several ranks), [1] spare, [2, 2 + 256) chunk counters of the A sum, [SYNC_ZM, SYNC_ZM + G) the
 // per-shard Z-operator counters (the fused W pass draws Z once its shard's operators are out)
@@ -364,6 +379,11 @@ void launch_pc_mean(const Dims &d, const Bufs &b, const PrecMean &pm, int nslots
 // pc.PC += (1 / effsamp) sum_s R(s) and pc.PC2 += (1 / effsamp) sum_s R(s).^2 over the batch's nslots samples
 void launch_partial_corr(const Dims &d, const Bufs &b, const PrecMean &pm, const PartialCorr &pc, const double *wslot,
                          int nslots, int B, double inv_eff, hipStream_t s);
+// regression.hip, behind launch_precision_panels and BEFORE launch_partial_corr (which scales pm.pfac in place) on
+// the same stream: the batch's nslots samples one by one, in slot order, into rg's six sums; pm.pfac, Lb and wslot
+// are only read
+void launch_regression(const Dims &d, const Bufs &b, const PrecMean &pm, const Regress &rg, const double *Lb,
+                       const double *wslot, int nslots, int B, hipStream_t s);
 // corr.hip, on the assembly stream: cr.cscale and cr.H / cr.H2 of the batch's nslots samples (k_corr_scale), then
 // cr.C += (1 / effsamp) sum_s R(s) and cr.C2 += (1 / effsamp) sum_s R(s).^2 (k_corr); Lb and wslot are only read
 void launch_corr(const Dims &d, const Bufs &b, const Corr &cr, const double *Lb, const double *wslot, int nslots,

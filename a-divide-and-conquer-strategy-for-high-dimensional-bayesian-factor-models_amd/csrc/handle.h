@@ -99,6 +99,11 @@ struct dcfm_handle {
     PartialCorr pc{};
     // posterior mean and second moment of the correlation matrix and of the communalities (DCFM_FLAG_CORR, corr.hip)
     Corr cr{};
+    // posterior moments of the regression coefficients (DCFM_FLAG_REGRESSION, dcfm_set_regression, regression.hip):
+    // one allocation, null when off; reg_n the saved samples the accumulators hold
+    void *reg_mem = nullptr;
+    Regress rg{};
+    int64_t reg_n = 0;
     bool prof = false;
     uint32_t prof_mask = 0;       // kernel ids (bit DCFM_K_*) timed with events
     int prof_stride = 1;          // time one in prof_stride launches of each (dcfm_set_profiling_stride)

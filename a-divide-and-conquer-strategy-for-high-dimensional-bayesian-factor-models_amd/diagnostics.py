@@ -232,3 +232,25 @@ def partial_correlation_edges(mean, sd, z=1.96, min_abs=0.0) -> dict:
     e = e & e.T
     e[np.diag_indices_from(e)] = False
     return {"z": zs, "edges": e}
+
+
+def regression_summary(coef, coef_sd, z=1.96) -> dict:
+    """Selected predictors of a factor regression from the posterior mean and standard deviation of its
+    coefficients (``Sampler.regression()``'s ``coef`` / ``coef_sd``, or ``divideconquer(..., regress=cols)``), both
+    (p, q), one column per response.  Returns ``{"z": mean / sd (signed), "selected": bool (p, q), "predictors":
+    a list of q index arrays}``: ``z`` is +-inf where sd == 0 and mean != 0 and NaN where either input is NaN or
+    both are 0 (the rows of the responses and of dropped columns); ``selected[a, j]`` holds where ``|z| >= z``,
+    a NaN selects nothing, and ``predictors[j]`` lists the selected rows of response j by decreasing ``|z|``."""
+    coef, coef_sd = np.asarray(coef, dtype=np.float64), np.asarray(coef_sd, dtype=np.float64)
+    if coef.ndim == 1:
+        coef, coef_sd = coef[:, None], coef_sd.reshape(-1, 1)
+    if coef.ndim != 2 or coef_sd.shape != coef.shape:
+        raise ValueError(f"coef and coef_sd must both be (p, q), got {coef.shape} and {coef_sd.shape}")
+    with np.errstate(divide="ignore", invalid="ignore"):
+        zs = coef / coef_sd
+        sel = np.abs(zs) >= z
+    pred = []
+    for j in range(coef.shape[1]):
+        idx = np.flatnonzero(sel[:, j])
+        pred.append(idx[np.argsort(-np.abs(zs[idx, j]), kind="stable")])
+    return {"z": zs, "selected": sel, "predictors": pred}

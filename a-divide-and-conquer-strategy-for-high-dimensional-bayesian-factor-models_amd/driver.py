@@ -205,7 +205,7 @@ def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hy
                   init_draws=None, iter_draws=None, nranks=1, rank=0, device=0, comm_uid=None,
                   asm_batch=0, return_info=False, device_ingest=True, device_init=True, return_sd=False,
                   n_components=0, rhs=None, probes=None, precision_probes=None, return_precision=False, loglik=False,
-                  predict=None, impute=False, return_partial=False, return_corr=False):
+                  predict=None, impute=False, return_partial=False, return_corr=False, regress=None):
     """Sigmaout = divideconquer(Y,g,k,BURNIN,MCMC,thin,rho)   (divideconquer.m:1).
 
     ``device_ingest`` (default): the zero-column scan and the partition/standardisation
@@ -322,6 +322,16 @@ def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hy
     with sd 0; with several ranks every rank fills in the entries of its own shards.  With ``predict`` the
     training moments used for the new rows are the observed-entry ones.  Not together with ``loglik``
     (ValueError): that would be the likelihood of the completed data.
+
+    ``regress``: up to 32 distinct column indices of Y (0-based, the input's column order): the responses of a
+    Bayesian factor regression on all the other columns.  They are taken into Sigmaout's coordinates (a response
+    that is a dropped all-zero column raises ValueError) and the posterior moments of the per-sample coefficients
+    ``Sigma_OO(s)^-1 Sigma_OR(s)``, of the residual covariance and of R^2 are accumulated on the device
+    (DCFM_FLAG_REGRESSION, Sampler.set_regression).  A dict ``{"coef", "coef_sd", "intercept", "resid_cov",
+    "resid_cov_sd", "r2", "r2_sd", "count", "responses"}`` is appended after the ``impute`` dict (if requested) and
+    before info, in the data's units and the input's column order (``unstandardize_regression``): coef and coef_sd
+    (p_orig, q), ``y[:, responses[j]] ~ intercept[j] + y @ coef[:, j]``, with 0 in the rows of the responses and of
+    the dropped columns.
     """
     t0 = time.perf_counter()                                     # dc:29 tic
     if impute and loglik:
@@ -348,12 +358,20 @@ def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hy
     elif not device_ingest:
         Yd = partition_standardize(Yk, g, np.asarray(init.varind))
     state = None if on_device_init else initial_state(n, P, K, g, rho, hyper, init)
+    resp = None
+    if regress is not None:                                      # the responses in Sigmaout's coordinates
+        rc = np.asarray(regress, dtype=np.int64).reshape(-1)
+        where = {int(c): a for a, c in enumerate(output_columns(keep, init.varind))}
+        gone = [int(c) for c in rc if int(c) not in where]
+        if gone:
+            raise ValueError(f"regress: columns {gone} of Y are all zero (dropped, dc:36-39) or out of range")
+        resp = np.array([where[int(c)] for c in rc], dtype=np.int64)
     gl = g // nranks
     s0 = rank * gl
     smp = Sampler(n, P, g, K, rho, BURNIN, MCMC, thin, hyper=hyper, seed=seed, nranks=nranks,
                   rank=rank, device=device, inject_draws=iter_draws is not None, asm_batch=asm_batch,
                   sigma_m2=return_sd, precision_mean=return_precision, partial_corr=return_partial,
-                  corr=return_corr)
+                  corr=return_corr, regression=resp is not None)
     try:
         if nranks > 1:
             if comm_uid is None:
@@ -382,6 +400,8 @@ def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hy
             cmean, csd = observed_moments(Yraw) if impute else column_moments(Yraw)
             Ystd, obs_in = standardize_rows(predict[0], predict[1], cmean, csd, keep, init.varind)
             smp.set_predict(Ystd, obs_in)
+        if resp is not None:
+            smp.set_regression(resp)
         smp.run(1, N)                                            # dc:90-197
         Sigmaout = smp.get_sigma()
         Sigmasd = smp.get_sigma_moment("sd") if return_sd else None
@@ -431,6 +451,11 @@ def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hy
             Yraw = np.asarray(Y, dtype=np.float64)
             omean, osd = observed_moments(Yraw)
             imp = unstandardize_imputation(smp.imputed(), Yraw, omean, osd, keep, init.varind, s0)
+        reg = None
+        if resp is not None:
+            Yraw = np.asarray(Y, dtype=np.float64)
+            rmean, rsd = observed_moments(Yraw) if impute else column_moments(Yraw)
+            reg = unstandardize_regression(smp.regression(), rmean, rsd, keep, init.varind, Yraw.shape[1])
     finally:
         smp.close()
     elapsed = time.perf_counter() - t0                           # dc:200 toc
@@ -455,6 +480,8 @@ def divideconquer(Y, g, k, BURNIN, MCMC, thin, rho, *, seed=0, hyper: Hyper = Hy
         out += (prd,)
     if impute:
         out += (imp,)
+    if regress is not None:
+        out += (reg,)
     if return_info:
         out += ({"varind": np.asarray(init.varind), "keep": keep, "n": n, "p": p, "P": P,
                  "K": K, "N": N, "seconds": elapsed},)
@@ -501,6 +528,31 @@ def unstandardize_prediction(pred, mean, sd, keep, varind, p_orig) -> dict:
         if f == "mean":
             v = v + mean[cols][:, None]
         out[f] = unpermute_vectors(v, keep, varind, p_orig).T.copy()
+    return out
+
+
+def unstandardize_regression(reg, mean, sd, keep, varind, p_orig, fill=0.0) -> dict:
+    """``Sampler.regression()``'s dict (standardised, Sigmaout's order) in the data's units and the input's column
+    order.  With sd_a the training columns' standard deviations and r_j the responses, a standardised coefficient
+    b_aj (y_rj / sd_rj ~ sum_a b_aj y_a / sd_a) becomes ``coef[a, j] = b_aj sd_rj / sd_a`` and its SD scales the
+    same way; ``intercept[j] = mean_rj - sum_a coef[a, j] mean_a``; resid_cov and its SD are scaled by sd_R on both
+    sides; R^2 does not change with the columns' scaling.  coef and coef_sd are (p_orig, q); dropped all-zero
+    columns get ``fill``.  ``responses`` are the responses' columns of Y."""
+    mean, sd = np.asarray(mean, dtype=np.float64), np.asarray(sd, dtype=np.float64)
+    cols = output_columns(keep, varind)
+    r = np.asarray(reg["responses"], dtype=np.int64)
+    sdk, sdr = sd[cols], sd[cols[r]]
+    scale = sdr[None, :] / sdk[:, None]
+    coef = np.asarray(reg["coef"], dtype=np.float64) * scale
+    out = {"coef": unpermute_vectors(coef, keep, varind, p_orig, fill=fill),
+           "coef_sd": unpermute_vectors(np.asarray(reg["coef_sd"], dtype=np.float64) * scale, keep, varind, p_orig,
+                                        fill=fill),
+           "intercept": mean[cols[r]] - mean[cols] @ coef,
+           "resid_cov": np.asarray(reg["resid_cov"], dtype=np.float64) * np.outer(sdr, sdr),
+           "resid_cov_sd": np.asarray(reg["resid_cov_sd"], dtype=np.float64) * np.outer(sdr, sdr),
+           "r2": np.asarray(reg["r2"], dtype=np.float64).copy(),
+           "r2_sd": np.asarray(reg["r2_sd"], dtype=np.float64).copy(),
+           "count": reg["count"], "responses": cols[r].copy()}
     return out
 
 

@@ -41,7 +41,7 @@ class Sampler:
 
     def __init__(self, n, P, g, K, rho, burnin, mcmc, thin, *, hyper: Hyper = Hyper(), seed=0,
                  nranks=1, rank=0, device=0, inject_draws=False, asm_batch=0, flags=0, sigma_m2=False,
-                 precision_mean=False, partial_corr=False, corr=False):
+                 precision_mean=False, partial_corr=False, corr=False, regression=False):
         self.lib = _abi.load_library()
         cfg = _abi.DcfmConfig()
         cfg.n, cfg.P, cfg.g, cfg.K = int(n), int(P), int(g), int(K)
@@ -55,7 +55,8 @@ class Sampler:
                      (_abi.DCFM_FLAG_SIGMA_M2 if sigma_m2 else 0) |
                      (_abi.DCFM_FLAG_PRECISION_MEAN if precision_mean else 0) |
                      (_abi.DCFM_FLAG_PARTIAL_CORR if partial_corr else 0) |
-                     (_abi.DCFM_FLAG_CORR if corr else 0) | int(flags))
+                     (_abi.DCFM_FLAG_CORR if corr else 0) |
+                     (_abi.DCFM_FLAG_REGRESSION if regression else 0) | int(flags))
         cfg.asm_batch = int(asm_batch)
         self.cfg = cfg
         h = C.c_void_p()
@@ -614,6 +615,44 @@ class Sampler:
         vb = np.maximum(m2 - mean * mean, 0.0)
         return {"mean": mean, "sd_between": np.sqrt(vb), "cvar": cvar, "sd_total": np.sqrt(cvar[:, None] + vb),
                 "maha": maha, "logdet": ld, "count": S}
+
+    # -- regression of a few variables on all the others ---------------------------------
+    def set_regression(self, responses):
+        """Accumulate, from the next run on, the posterior moments of the coefficients of the regression of the
+        variables ``responses`` (up to 32 distinct 0-based indices in Sigmaout's permuted, standardised
+        coordinates) on all the others (dcfm_set_regression; needs ``Sampler(..., regression=True)``).  Calling it
+        again replaces the set and zeroes the accumulators; ``None`` or an empty list turns it off.  Every rank
+        passes the same set."""
+        r = np.ascontiguousarray(np.asarray([] if responses is None else responses, dtype=np.int64).reshape(-1))
+        self._check(self.lib.dcfm_set_regression(
+            self.h, r.ctypes.data_as(C.POINTER(C.c_int64)) if r.size else None, int(r.size)))
+        self._reg_q, self._reg_resp = int(r.size), r.copy()
+
+    def regression_raw(self):
+        """``(coef, coef_m2, rcov, rcov_m2, r2, r2_m2, count)`` exactly as dcfm_get_regression returns them: coef
+        and coef_m2 (p, q), rcov and rcov_m2 (q, q), r2 and r2_m2 (q,); all zeros with count 0."""
+        q, p = getattr(self, "_reg_q", 0), self.P * self.g
+        cnt = C.c_int64(0)
+        coef, coef2 = (np.zeros((p, q), dtype=np.float64, order="F") for _ in range(2))
+        rcov, rcov2 = (np.zeros((q, q), dtype=np.float64, order="F") for _ in range(2))
+        r2, r22 = np.zeros(q, dtype=np.float64), np.zeros(q, dtype=np.float64)
+        self._check(self.lib.dcfm_get_regression(self.h, _ptr(coef), _ptr(coef2), _ptr(rcov), _ptr(rcov2), _ptr(r2),
+                                                 _ptr(r22), C.byref(cnt)))
+        return coef, coef2, rcov, rcov2, r2, r22, int(cnt.value)
+
+    def regression(self) -> dict:
+        """The regression accumulated so far, in standardised, permuted coordinates: ``coef`` (p, q) the posterior
+        mean of B(s) = Sigma_OO(s)^-1 Sigma_OR(s) (rows of the responses exactly 0: E[y_R | y_O] = coef' y),
+        ``coef_sd`` its per-coefficient posterior SD, ``resid_cov`` / ``resid_cov_sd`` (q, q) those of the residual
+        covariance Cov[y_R | y_O, Sigma(s)], ``r2`` / ``r2_sd`` (q,) those of 1 - C_jj / Sigma_jj, and ``count``, the
+        samples accumulated (the divisor).  Each SD is sqrt(max(0, m2 - mean^2)).  ``responses`` repeats the set."""
+        coef, coef2, rcov, rcov2, r2, r22, S = self.regression_raw()
+
+        def sd(m, m2):
+            return np.sqrt(np.maximum(m2 - m * m, 0.0))
+        return {"coef": coef, "coef_sd": sd(coef, coef2), "resid_cov": rcov, "resid_cov_sd": sd(rcov, rcov2),
+                "r2": r2, "r2_sd": sd(r2, r22), "count": S,
+                "responses": getattr(self, "_reg_resp", np.zeros(0, dtype=np.int64)).copy()}
 
     # -- missing training data -----------------------------------------------------------
     def set_missing(self, mask, capacity=None):

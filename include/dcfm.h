@@ -90,6 +90,12 @@ extern "C" {
                                         array, two p-vectors and the two kernels of corr.hip per flush),
                                         for dcfm_get_corr[_cols] and dcfm_get_communality; off: nothing
                                         is allocated or launched                           */
+#define DCFM_FLAG_REGRESSION   0x800u  /* allow dcfm_set_regression: the per-sample omega slots, the factor
+                                        buffer and the panel scratch that DCFM_FLAG_PARTIAL_CORR alone
+                                        allocates (no p x p accumulator: dcfm_sigma_block's bytes do not
+                                        change); the panel kernels and the two kernels of regression.hip
+                                        run per flush once a response set is given; off: nothing is
+                                        allocated or launched                              */
 
 typedef struct dcfm_handle dcfm_handle;
 
@@ -558,6 +564,51 @@ int  dcfm_get_loglik(dcfm_handle *h, double *maha, double *logdet, int64_t *coun
 int  dcfm_set_predict(dcfm_handle *h, const double *Ynew, const uint8_t *observed, int32_t nt, int64_t capacity);
 int  dcfm_get_predict(dcfm_handle *h, double *mean, double *m2, double *cvar, double *maha, double *logdet,
                       int64_t *count);
+
+/* ---- regression of a few variables on all the others: posterior mean and SD of the coefficients ----------------
+ * Bayesian factor regression (DCFM_FLAG_REGRESSION at dcfm_create, else DCFM_ERR_INVALID).  The response set is
+ * R = (r_1 .. r_q), distinct indices in Sigmaout's permuted, standardised coordinates, O its complement.  Per saved
+ * sample s, with Theta(s) = Sigma(s)^-1 of the per-sample matrix of dc:182-192,
+ *   T(s) = Theta(s)[:, R]  (p x q),   Q(s) = (T(s)[R, :] + T(s)[R, :]') / 2,
+ *   C(s) = Q(s)^-1 = Cov[y_R | y_O, Sigma(s)], the residual covariance (one triangle computed, then mirrored),
+ *   B(s) = -T(s) C(s) with the q rows a in R set to exactly 0: E[y_R | y_O, Sigma(s)] = B(s)' y and
+ *          B(s)[O, :] = Sigma_OO(s)^-1 Sigma_OR(s), the coefficients of the regression of y_R on y_O,
+ *   R2_j(s) = 1 - C(s)_jj / Sigma(s)_{r_j r_j},  Sigma(s)_aa = |Lambda_a(s)|^2 + omega_a(s).
+ * The device keeps the sums over the saved samples of B, B.^2 (p x q), C, C.^2 (q x q), R2 and R2.^2 (q).  B(s) is a
+ * ratio of entries of Theta(s): its mean is not the ratio of dcfm_get_precision_mean's entries, and it comes with a
+ * second moment, hence a per-coefficient posterior SD sqrt(max(0, m2 - mean^2)).  The columns of Theta(s) come from
+ * the thin factor panels of the precision mean (Theta(s) is block-diagonal plus low rank): q K-length dot products
+ * per row and sample and a q x q Gauss-Jordan inversion per sample, no p x p factorisation.  An entry is accurate
+ * to first order in eps cond(Sigma(s)), as the precision mean.  Accumulated at every flush on the assembly stream,
+ * one sample at a time in sample order from sums loaded first and stored once; no floating-point atomics, fixed
+ * summation orders: the same inputs give the same bits whatever asm_batch is and however the chain is cut into
+ * dcfm_run calls.  Booked under DCFM_K_ASSEMBLE.  Independent of every other read-out: none changes another's bits.
+ *
+ * dcfm_set_regression: resp holds q 0-based indices, 0 <= q <= 32 and q < p.  It takes effect from the next dcfm_run;
+ * a second call replaces R and zeroes the accumulators and the count; q == 0 (resp may be NULL) turns the feature off
+ * and frees its buffers.  Not collective, but every rank must pass the same resp: every rank holds the gathered
+ * panels of all g shards and accumulates all p rows (bitwise equal on all ranks).
+ * Device bytes: with the flag, the factor buffer p x 4 round_up(asm_batch K, 16) doubles, the (2 g + 1) asm_batch K^2
+ * scratch and the omega slots 2 p asm_batch (all shared with DCFM_FLAG_PRECISION_MEAN / _PARTIAL_CORR); with a
+ * response set, 8 (2 p q + 2 (q^2 + q) + asm_batch (q^2 + q + (1 + t) K4 qp)) + 4 (2 q + t + 1 + g), t <= q the shards
+ * that hold a response, K4 = K rounded up to 4, qp = q to 16.  LDS: 9.1 KiB static (Q(s) and the inversion's
+ * multipliers) in the per-sample kernel, 16.5 KiB static (four 16 x 32 tiles of B(s)) in the pass over the rows.
+ * Errors (DCFM_ERR_INVALID, the setting made before stays as it was): NULL handle ("null handle"), the flag not set
+ * (the message names DCFM_FLAG_REGRESSION), NULL resp with q > 0 ("null argument"), q outside 0..32 or q >= p, an index
+ * outside [0, p), a duplicate index.
+ *
+ * dcfm_get_regression: count (required) receives the number of samples accumulated; every other output is nullable.
+ * coef and coef_m2 are p x q column-major: sum B / count and sum B.^2 / count (count is the number of samples
+ * actually accumulated, the population form of dcfm_get_predict, not effsamp), exactly 0 in the rows of R; rcov and
+ * rcov_m2 are q x q (symmetric bit for bit), r2 and r2_m2 have q entries.  Blocks (synchronises the sweep and the
+ * assembly streams) and does not disturb a later dcfm_run.  With nothing set or no sample accumulated yet *count = 0,
+ * DCFM_OK, and nothing else is written.  Not collective: `out` pointers must be non-NULL on every rank that wants the
+ * data.  After a run that ended in DCFM_ERR_NUMERIC it returns what the device holds (no stage takes a
+ * data-dependent trip count: a NaN runs through).  Errors (DCFM_ERR_INVALID): NULL handle ("null handle"), NULL
+ * count ("null argument"). */
+int  dcfm_set_regression(dcfm_handle *h, const int64_t *resp, int32_t q);
+int  dcfm_get_regression(dcfm_handle *h, double *coef, double *coef_m2, double *rcov, double *rcov_m2, double *r2,
+                         double *r2_m2, int64_t *count);
 
 /* ---- missing training data: an on-device imputation step ------------------------------------------------------
  * Given eta, Lambda and ps every missing entry of the training matrix is conditionally independent,

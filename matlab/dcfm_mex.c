@@ -7,7 +7,7 @@
  * on the GPU).  Commands:
  *   h = dcfm_mex('create', cfg)           cfg fields n P g K rho burnin mcmc thin as bs df ad1
  *                                         bd1 ad2 bd2 seed device inject asm_batch sigma_m2
- *                                         precision_mean partial_corr corr
+ *                                         precision_mean partial_corr corr regression
  *   dcfm_mex('set_data', h, Yd)           Yd n x P x g (dc:49-59 done by the caller)
  *   dcfm_mex('set_data_raw', h, Y0, cols) raw n x p0 data + int64 0-based columns (dc:48-59 on GPU)
  *   dcfm_mex('set_state', h, Lambda, ps, omega, psijh, Plam, X, Z, delta, tauh)
@@ -81,6 +81,14 @@
  *                                         Yd and Yd.^2), nvar P x g the average 1 / ps_j of the columns with a missing
  *                                         entry (total variance nvar + m2 - mean.^2), count the samples accumulated
  *                                         (count 0: empty arrays)
+ *   dcfm_mex('set_regression', h, resp)   regress the variables resp (1-based indices in Sigmaout's coordinates, at most
+ *                                         32, distinct; [] turns it off) on all the others under every saved sample
+ *                                         of later runs (needs cfg.regression = 1)
+ *   [coef, coef_m2, rcov, rcov_m2, r2, r2_m2, count] = dcfm_mex('regression', h)   the accumulated regression: coef
+ *                                         and coef_m2 p x q (the averages of the per-sample coefficients
+ *                                         Sigma_OO \ Sigma_OR and of their squares; rows resp are 0), rcov and
+ *                                         rcov_m2 q x q (the residual covariance), r2 and r2_m2 q x 1, count the samples
+ *                                         accumulated (count 0: empty arrays); SD = sqrt(max(0, m2 - mean.^2))
  *   e = dcfm_mex('error', h, U, s, iters)[||S-S0||_F, ||S0||_F, ||S-S0||_2] vs S0 = UU' + diag(s)
  *   dcfm_mex('set_trace', h, cap); T = dcfm_mex('get_trace', h)     chain trace (count x 4)
  *   dcfm_mex('destroy', h)
@@ -103,6 +111,7 @@ typedef struct {
     int64_t nv;                /* width of the probe block the library holds (0: none) */
     int64_t pnv;               /* width of the precision-probe block the library holds */
     int64_t pnt;               /* new rows of the prediction the library holds */
+    int64_t rq;                /* responses of the regression the library holds */
 } slot;
 static slot S[NSLOT];          /* handles live across calls */
 
@@ -168,6 +177,7 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         if (fld(s, "precision_mean", 0) != 0) c.flags |= DCFM_FLAG_PRECISION_MEAN;
         if (fld(s, "partial_corr", 0) != 0) c.flags |= DCFM_FLAG_PARTIAL_CORR;
         if (fld(s, "corr", 0) != 0) c.flags |= DCFM_FLAG_CORR;
+        if (fld(s, "regression", 0) != 0) c.flags |= DCFM_FLAG_REGRESSION;
         c.asm_batch = (int32_t)fld(s, "asm_batch", 0);
         int i = 0;
         while (i < NSLOT && S[i].h) ++i;
@@ -177,7 +187,7 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
             mexErrMsgIdAndTxt("dcfm:create", "%s", dcfm_last_error(NULL));
         }
         S[i].n = c.n; S[i].P = c.P; S[i].g = c.g; S[i].K = c.K;
-        S[i].mcmc = c.mcmc; S[i].thin = c.thin; S[i].nv = 0; S[i].pnv = 0; S[i].pnt = 0;
+        S[i].mcmc = c.mcmc; S[i].thin = c.thin; S[i].nv = 0; S[i].pnv = 0; S[i].pnt = 0; S[i].rq = 0;
         mexLock();
         plhs[0] = mxCreateDoubleScalar(i);
     } else if (!strcmp(cmd, "set_data")) {
@@ -602,6 +612,47 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         o[3] = mxCreateDoubleScalar((double)cnt);
         if (cnt > 0) ck(t->h, dcfm_get_imputed(t->h, mxGetDoubles(o[0]), mxGetDoubles(o[1]), mxGetDoubles(o[2]), &cnt));
         for (int i = 0; i < 4; ++i)
+            if (i == 0 || i < nlhs) plhs[i] = o[i];
+            else mxDestroyArray(o[i]);
+    } else if (!strcmp(cmd, "set_regression")) {     /* dcfm_mex('set_regression', h, resp) */
+        nargs(nrhs, 3, cmd);
+        /* the argument that needs no handle first: a malformed call never reaches the library */
+        const mxArray *r = prhs[2];
+        if (!mxIsDouble(r) || mxIsComplex(r) || mxGetNumberOfElements(r) > 32)
+            mexErrMsgIdAndTxt("dcfm:arg", "resp must be a real double vector of at most 32 1-based indices, or empty");
+        const int32_t q = (int32_t)mxGetNumberOfElements(r);
+        int64_t resp[32];
+        for (int32_t j = 0; j < q; ++j) {
+            const double v = mxGetDoubles(r)[j];
+            if (!(v >= 1.0 && v <= 2147483647.0) || v != (double)(int64_t)v)
+                mexErrMsgIdAndTxt("dcfm:arg", "resp must hold positive integers (1-based indices)");
+            resp[j] = (int64_t)v - 1;
+        }
+        slot *t = get(prhs[1]);
+        for (int32_t j = 0; j < q; ++j)
+            if (resp[j] >= t->P * t->g)
+                mexErrMsgIdAndTxt("dcfm:arg", "resp must lie in 1 .. p = %lld", (long long)(t->P * t->g));
+        ck(t->h, dcfm_set_regression(t->h, q > 0 ? resp : NULL, q));
+        t->rq = q;
+    } else if (!strcmp(cmd, "regression")) {         /* [coef, coef_m2, rcov, rcov_m2, r2, r2_m2, count] = ... */
+        nargs(nrhs, 2, cmd);
+        slot *t = get(prhs[1]);
+        int64_t cnt = 0;
+        ck(t->h, dcfm_get_regression(t->h, NULL, NULL, NULL, NULL, NULL, NULL, &cnt));
+        const mwSize on = cnt > 0 ? 1 : 0;           /* the library writes nothing while the count is 0 */
+        const mwSize p = on * (mwSize)(t->P * t->g), q = on * (mwSize)t->rq;
+        mxArray *o[7];                               /* the sizes the library writes */
+        o[0] = mxCreateDoubleMatrix(p, q, mxREAL);
+        o[1] = mxCreateDoubleMatrix(p, q, mxREAL);
+        o[2] = mxCreateDoubleMatrix(q, q, mxREAL);
+        o[3] = mxCreateDoubleMatrix(q, q, mxREAL);
+        o[4] = mxCreateDoubleMatrix(q, on, mxREAL);
+        o[5] = mxCreateDoubleMatrix(q, on, mxREAL);
+        o[6] = mxCreateDoubleScalar((double)cnt);
+        if (cnt > 0)
+            ck(t->h, dcfm_get_regression(t->h, mxGetDoubles(o[0]), mxGetDoubles(o[1]), mxGetDoubles(o[2]),
+                                         mxGetDoubles(o[3]), mxGetDoubles(o[4]), mxGetDoubles(o[5]), &cnt));
+        for (int i = 0; i < 7; ++i)
             if (i == 0 || i < nlhs) plhs[i] = o[i];
             else mxDestroyArray(o[i]);
     } else if (!strcmp(cmd, "destroy")) {

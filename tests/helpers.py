@@ -72,7 +72,57 @@ def loading_backward_error(lam_mat, Q, b, L, z):
     return float(np.max(np.linalg.norm(r, axis=-1) / den))
 
 
-def stagewise_errors(start, got, Yd, rho, hyper, draws, check_lambda=None):
+# The bars of loading_scaled_backward_error, per class of cond_2(D Q_j D): 8 x the worst the reference itself
+# reads over every k_paths case, flat-start case and replay layout (the oracle's two flavours and a solve with
+# the factor of an entrywise K eps perturbation of Q_j).  tests/test_loading_measure.py measures that on the CPU
+# and holds the constants against it; no device figure enters.
+SBW_COND_WELL = 1e3
+SBW_TOL_WELL = 8e-14          # rows with cond_2(D Q_j D) <= SBW_COND_WELL
+SBW_TOL = 7e-13               # the other rows
+
+
+def loading_scaled_bars(cond):
+    """The bar of every row from its cond_2(D Q_j D) (taken from the oracle's Q_j on the host)."""
+    return np.where(np.asarray(cond) <= SBW_COND_WELL, SBW_TOL_WELL, SBW_TOL)
+
+
+class LoadingMeasure:
+    """Per-row diagonally scaled backward error of a loading draw.  With D = diag(Q_j)^-1/2 and
+    r = Q_j lam_j - b_j - L_j z_j:  || D r || / (|| D Q_j D ||_2 || D^-1 lam_j || + || D b_j || + || D L_j ||_2 || z_j ||).
+    loading_backward_error is relative to ||Q_j|| ||lam_j||, and at wide K ||Q_j|| is Plam's trailing diagonal
+    (tau_K ~ 2^K), so a relative error in the data part of a wide factor does not move it; D Q_j D has a unit
+    diagonal, so here every row and column of the system weighs the same (Van der Sluis: D is within sqrt(K) of
+    the best diagonal scaling).  The L_j z_j term takes the oracle's factor as data, and an implementation's own
+    backward-stable factor differs from it by the Cholesky factor's perturbation sensitivity, so a legitimate
+    result reads up to ~ K eps cond_2(D Q_j D); the bars (tests/test_loading_measure.py) are therefore per class
+    of cond_2(D Q_j D): `cond`, g x P.
+    The systems are g x P x ... (oracle.vectorised.loading_systems); their norms are taken once, and the object is
+    called with any number of candidate draws (P x K x g, MATLAB layout).  Returns the measure, g x P; with
+    `residual` also D r (g x P x K: which entries of a row miss)."""
+
+    def __init__(self, Q, b, L, z):
+        self.Q, self.b = Q, b
+        self.d = d = 1.0 / np.sqrt(np.diagonal(Q, axis1=-2, axis2=-1))      # g x P x K
+        ev = np.linalg.eigvalsh(d[..., :, None] * Q * d[..., None, :])      # D Q_j D is symmetric positive definite
+        self.nq, self.cond = ev[..., -1], ev[..., -1] / ev[..., 0]
+        self.Lz = np.einsum("mjkl,mjl->mjk", L, z)
+        # || D L_j ||_2 = || D Q_j D ||_2^(1/2): L_j is Q_j's Cholesky factor, (D L_j)(D L_j)' = D Q_j D
+        self.rhs = np.linalg.norm(d * b, axis=-1) + np.sqrt(self.nq) * np.linalg.norm(z, axis=-1)
+
+    def __call__(self, lam_mat, residual=False):
+        lam = np.moveaxis(np.asarray(lam_mat, dtype=np.float64), 2, 0)      # g x P x K
+        Dr = self.d * (np.einsum("mjkl,mjl->mjk", self.Q, lam) - self.b - self.Lz)
+        sbw = np.linalg.norm(Dr, axis=-1) / (self.nq * np.linalg.norm(lam / self.d, axis=-1) + self.rhs)
+        return (sbw, Dr) if residual else sbw
+
+
+def loading_scaled_backward_error(lam_mat, Q, b, L, z):
+    """LoadingMeasure of one draw: (measure, cond_2(D Q_j D)), both g x P."""
+    m = LoadingMeasure(Q, b, L, z)
+    return m(lam_mat), m.cond
+
+
+def stagewise_errors(start, got, Yd, rho, hyper, draws, check_lambda=None, scaled=False):
     """Stage-wise parity of one Gibbs iteration (absolute bars, no comparison of two
     implementations' rounding): from the oracle state `start` at the iteration's start,
       * the stages before the loading solve (Z, X, eta; dc:97-134) vs the oracle's, relative;
@@ -89,7 +139,8 @@ def stagewise_errors(start, got, Yd, rho, hyper, draws, check_lambda=None):
         (resid.hip header), e.g. 1.3e-10 at config c2's second iteration.
     `got` maps state fields to MATLAB-layout arrays (Sampler.get_state, or an oracle state's
     as_dict()).  Returns ({field: rel err}, lambda backward error, the oracle state after the
-    iteration with got's Lambda)."""
+    iteration with got's Lambda); with `scaled` a fourth value, loading_scaled_backward_error's per-row
+    (measure, cond_2(D Q_j D)) of the same systems, both g x P."""
     from oracle import vectorised as V
     D = V._as_data(Yd)
     st = start.copy()
@@ -100,6 +151,7 @@ def stagewise_errors(start, got, Yd, rho, hyper, draws, check_lambda=None):
         getattr(st, f)[...] = np.asarray(got[f], dtype=np.float64).reshape(getattr(st, f).shape)
     E, C, Q, b, L, z = V.loading_systems(st, D, draws)
     bw = loading_backward_error(got["Lambda"], Q, b, L, z)
+    sbw = loading_scaled_backward_error(got["Lambda"], Q, b, L, z) if scaled else None
     V.update_Lambda_psi_delta_ps(st, D, hyper, draws, lam_given=got["Lambda"])
     V.update_Plam(st)
     for f in ("psi", "delta", "tauh", "Plam"):
@@ -107,7 +159,7 @@ def stagewise_errors(start, got, Yd, rho, hyper, draws, check_lambda=None):
     F.update_ps(st, D.Yd, hyper, draws)      # dc:169-171 as written, on got's eta and Lambda
     for f in ("ps", "omega"):
         errs[f] = elem_rel_err(got[f], getattr(st, f))
-    return errs, bw, st
+    return (errs, bw, st, sbw) if scaled else (errs, bw, st)
 
 
 def elem_rel_err(a, b):

@@ -101,3 +101,33 @@ def case(K):
     c = make_case(n, P * g, g, K, seed=SEED)
     assert (c["n"], c["P"]) == (n, P), "preprocessing dropped a column"
     return c
+
+
+# ---- the flat-shrinkage start ---------------------------------------------------------------------------
+# At the default start tau_h = prod delta reaches 2e10 and Plam 1e11, so from K ~ 65 on the trailing 16 x 16
+# tiles of D Q_j D (D = diag(Q_j)^-1/2) are the identity to rounding: whatever the loading kernels multiply
+# there cannot change Lambda (tests/test_loading_measure.py shows it).  The flat start is the case's start
+# state with delta = 1, tauh = 1 and Plam = psi (a valid state: Plam = psi o tau), under which every tile of
+# the factor carries data (cond(Q_j) <= 310).  It is run for exactly ONE iteration: a second one from it is an
+# excursion of the reference itself (max|X| 1.3e4 at K = 33; the oracle's chol fails at K = 40).
+FLAT_NARROW = [16, 20, 23, 24, 30, 32]          # one K of every narrow KE class that pairs pivots
+FLAT_CASES = FLAT_NARROW + WIDE
+FLAT_MODE_CASES = EXTRA_MODE_CASES               # these also under DCFM_FLAG_GUARD_ALL and DCFM_FLAG_EXACT_RESIDUAL
+FLAT_ALL = sorted(set(FLAT_CASES) | set(FLAT_MODE_CASES))     # every K the reference is checked at (K = 12 joins)
+FLAT_BURNIN, FLAT_MCMC, FLAT_THIN = 0, 1, 1     # the one iteration is the one saved sample
+
+
+def flat_start(K):
+    """The oracle state of case(K)'s start with the shrinkage switched off (a fresh copy)."""
+    st = case(K)["st"].copy()
+    st.delta[...] = 1.0
+    st.tauh[...] = 1.0
+    st.Plam[...] = st.psi
+    return st
+
+
+def flat_case(K):
+    """case(K) with flat_start(K) as its start state; data, draws and shape are the case's own."""
+    c = dict(case(K))
+    c["st"] = flat_start(K)
+    return c

@@ -110,8 +110,12 @@ def test_fused_run_in_x_excursion_regime(dcfm, record_property):
 
     worst = {}
     for it in range(1, N + 1):
-        errs, bw, ref = stagewise_errors(_as_oracle(states[it - 1]), states[it], c["Yd"], c["rho"], c["hyper"],
-                                         c["src"].iteration(it))
+        errs, bw, ref, (sbw, cond) = stagewise_errors(_as_oracle(states[it - 1]), states[it], c["Yd"], c["rho"],
+                                                      c["hyper"], c["src"].iteration(it), scaled=True)
+        # the scaled loading measure: recorded and printed with the rest, not asserted (the excursion's states
+        # have not been measured against the reference: tests/test_loading_measure.py)
+        worst["lambda_sbw"] = max(worst.get("lambda_sbw", 0.0), float(sbw.max()))
+        worst["cond_dqd"] = max(worst.get("cond_dqd", 0.0), float(cond.max()))
         # ps / omega: 1e-10 per row, or -- where the excursion makes dc:169's residual itself cancel -- the
         # residual's own rounding bound at this state (helpers.residual_rounding_bound), if larger
         bound = residual_rounding_bound(states[it], c["Yd"]).T

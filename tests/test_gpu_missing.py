@@ -145,12 +145,15 @@ def test_the_sweep_reads_the_completed_data(dcfm, name, flags):
     c = _case(name)
     worst, worst_bw = {}, 0.0
     for it, (Y0, st0, got, _) in enumerate(_stepped(dcfm, name, "random", flags), start=1):
-        errs, bw, _ = stagewise_errors(_as_oracle(st0), got, Y0, c["rho"], c["hyper"], c["src"].iteration(it))
+        errs, bw, _, (sbw, cond) = stagewise_errors(_as_oracle(st0), got, Y0, c["rho"], c["hyper"],
+                                                    c["src"].iteration(it), scaled=True)
         for f, e in errs.items():
             worst[f] = max(worst.get(f, 0.0), e)
         worst_bw = max(worst_bw, bw)
+        # the scaled loading measure is printed beside the normwise one, not asserted (these states have not been
+        # measured against the reference: tests/test_loading_measure.py)
         print(f"MISSING_STAGEWISE {name} flags {flags:#x} it {it}:", {k: f"{v:.2e}" for k, v in errs.items()},
-              f"bw {bw:.2e}")
+              f"bw {bw:.2e} sbw {sbw.max():.2e} cond(DQD) <= {cond.max():.2e}")
         for f, e in errs.items():
             assert e < TOL, f"iteration {it}: stage {f} rel err {e:.3e} (bar {TOL:.0e})"
         assert bw <= BW_TOL, f"iteration {it}: loading backward error {bw:.3e} (bar {BW_TOL:.0e})"

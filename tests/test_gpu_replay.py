@@ -21,7 +21,8 @@ import numpy as np
 import pytest
 
 import replay_cases as rc
-from helpers import STATE_CMP, as_oracle_state as _as_oracle, residual_rounding_bound, scaled_rel_err, stagewise_errors
+from helpers import (SBW_COND_WELL, SBW_TOL_WELL, STATE_CMP, as_oracle_state as _as_oracle, residual_rounding_bound, scaled_rel_err,
+                     stagewise_errors)
 
 pytestmark = pytest.mark.gpu
 
@@ -83,7 +84,9 @@ def _assert_state_equal(got, want, what):
 def test_stepped_chain_is_the_references(dcfm, layout, record_property):
     """Measured on the MI355X (worst over the 27 iterations; X, Z, eta, psi, delta, tauh, Plam normwise, ps /
     omega per row against max(1e-10, the residual's rounding bound), loading rows by backward error): see
-    DESIGN.md section 2, "Replay invariants"."""
+    DESIGN.md section 2, "Replay invariants".  Every row of these layouts has cond(D Q_j D) <= 1e3 in every
+    iteration (tests/test_loading_measure.py: <= 9.6 on the reference's chain), so the diagonally scaled
+    backward error is held to SBW_TOL_WELL and the class itself is asserted."""
     from oracle import philox_ref as R
     c = rc.case(layout)
     states = _stepped(dcfm, layout)["states"]
@@ -94,19 +97,24 @@ def test_stepped_chain_is_the_references(dcfm, layout, record_property):
         got = states[it]
         xmax = float(np.abs(got["X"]).max())
         assert xmax < 10.0, f"iteration {it}: max|X| {xmax:.3g}: the chain left the stationary range"
-        errs, bw, ref = stagewise_errors(_as_oracle(states[it - 1]), got, c["Yd"], c["rho"], c["hyper"],
-                                         src.iteration(it))
+        errs, bw, ref, (sbw, cond) = stagewise_errors(_as_oracle(states[it - 1]), got, c["Yd"], c["rho"], c["hyper"],
+                                                      src.iteration(it), scaled=True)
         bound = residual_rounding_bound(got, c["Yd"]).T
         for f in ("ps", "omega"):
             worst[f + "_raw"] = max(worst.get(f + "_raw", 0.0), errs[f])
             errs[f] = scaled_rel_err(got[f], getattr(ref, f), bound, TOL)
         worst["xmax"] = max(worst.get("xmax", 0.0), xmax)
         worst["lambda_bw"] = max(worst.get("lambda_bw", 0.0), bw)
+        worst["lambda_sbw"] = max(worst.get("lambda_sbw", 0.0), float(sbw.max()))
+        worst["cond_dqd"] = max(worst.get("cond_dqd", 0.0), float(cond.max()))
         for f, e in errs.items():
             worst[f] = max(worst.get(f, 0.0), e)
         for f, e in errs.items():
             assert e < TOL, f"iteration {it}: stage {f} rel err {e:.3e} (bar {TOL:.0e})"
         assert bw <= BW_TOL, f"iteration {it}: loading backward error {bw:.3e} (bar {BW_TOL:.0e})"
+        assert cond.max() <= SBW_COND_WELL, f"iteration {it}: cond(DQD) {cond.max():.3e}: a row left the well class"
+        assert sbw.max() <= SBW_TOL_WELL, (f"iteration {it}: scaled loading backward error {sbw.max():.3e} at "
+                                           f"{np.unravel_index(np.argmax(sbw), sbw.shape)} (bar {SBW_TOL_WELL:.0e})")
     for f, e in worst.items():
         record_property(f"worst_{f}", e)
     print("REPLAY_STAGEWISE", layout, {k: f"{v:.2e}" for k, v in sorted(worst.items())})

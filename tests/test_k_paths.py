@@ -15,6 +15,11 @@ and the reference at every case.  No GPU.
      -- the same measurement the GPU test makes of the library.  Condition: <= 1e-12 on every field, loading
      backward error <= 1e-15, ps and omega finite and positive.  A case that misses it gets another n, not
      another bar.
+  4. The same at the flat start (k_paths.flat_case: delta = 1, tauh = 1, Plam = psi; one iteration, never
+     continued), where cond(Q_j) <= 310 makes a forward bar legitimate: the two flavours' Lambda agree to 1e-12
+     normwise, max|X| stays in the stationary range, and the case list has one K of every narrow class that
+     pairs pivots and every wide case.  The diagonally scaled loading measure, its bars and what the flat start
+     reaches are tests/test_loading_measure.py's.
 """
 import re
 from pathlib import Path
@@ -29,6 +34,8 @@ CSRC = next(Path(__file__).resolve().parents[1].glob("*_amd")) / "csrc"
 
 SELF_TOL = 1e-12      # faithful loop vs the vectorised stages, from the same start
 SELF_BW = 1e-15       # the faithful loop's own loading backward error
+FLAT_COND = 1e3       # cond(Q_j) at the flat start (measured <= 306, K = 88)
+FLAT_XMAX = 10.0      # max|X| after the flat start's one iteration (measured <= 3.04)
 
 
 def _text(name):
@@ -164,3 +171,49 @@ def test_reference_is_well_posed(K):
     for f, e in worst.items():
         assert e <= SELF_TOL, f"K = {K}: the oracle's two flavours differ in {f} by {e:.3e} (bar {SELF_TOL:.0e})"
     assert worst_bw <= SELF_BW, f"K = {K}: the faithful loop's loading backward error {worst_bw:.3e} (bar {SELF_BW:.0e})"
+
+
+def test_flat_cases_cover_the_pivot_pairing_classes():
+    assert set(kp.WIDE) <= set(kp.FLAT_CASES) and set(kp.FLAT_MODE_CASES) <= set(kp.CASES)
+    narrow = kp.members("lambda", kp.K_MIN, 32)
+    for ke, Ks in narrow.items():
+        if ke >= 16:                     # k_lambda<8> is tests/test_gpu_parity.py's; from KE 16 on pivots pair
+            assert set(Ks) & set(kp.FLAT_CASES), f"k_lambda<{ke}>: no flat-start case"
+    assert (kp.FLAT_BURNIN, kp.FLAT_MCMC, kp.FLAT_THIN) == (0, 1, 1)
+    st, flat = kp.case(23)["st"], kp.flat_start(23)
+    assert np.all(flat.delta == 1.0) and np.all(flat.tauh == 1.0) and np.array_equal(flat.Plam, flat.psi)
+    assert np.any(st.tauh != 1.0), "flat_start changed the shared case"
+    for f in ("Lambda", "ps", "omega", "psi", "X", "Z", "eta"):
+        assert np.array_equal(getattr(flat, f), getattr(st, f))
+
+
+@pytest.mark.parametrize("K", kp.FLAT_ALL, ids=kp.case_id)
+def test_flat_reference_is_well_posed(K):
+    from helpers import rel_err, stagewise_errors
+    from oracle import vectorised as V
+    c = kp.flat_case(K)
+    dr = c["src"].iteration(1)
+    ref = c["st"].copy()
+    assert not np.any(ref.Lambda)
+    F.gibbs_iteration(ref, c["Yd"], c["rho"], c["hyper"], dr)
+    errs, bw, _, (sbw, cond) = stagewise_errors(c["st"], ref.as_dict(), c["Yd"], c["rho"], c["hyper"], dr, scaled=True)
+    vec = V.gibbs_iteration(c["st"].copy(), c["Yd"], c["rho"], c["hyper"], dr)
+    fwd = rel_err(ref.Lambda, vec.Lambda)
+    D = V._as_data(c["Yd"])
+    st = c["st"].copy()
+    V.update_ZX(st, D, c["rho"], dr)
+    V.update_eta(st, c["rho"])
+    condQ = float(np.linalg.cond(V.loading_systems(st, D, dr)[2]).max())
+    xmax = float(np.abs(ref.X).max())
+    print("K_PATHS_FLAT_REFERENCE", kp.case_id(K), kp.shape(K), {f: f"{e:.2e}" for f, e in sorted(errs.items())},
+          f"lambda_bw {bw:.2e} lambda_sbw {sbw.max():.2e} cond(DQD) {cond.max():.3g} cond(Q) {condQ:.3g} "
+          f"Lambda forward {fwd:.2e} max|X| {xmax:.3g}")
+    for f in ("ps", "omega"):
+        v = getattr(ref, f)
+        assert np.all(np.isfinite(v)) and np.all(v > 0.0), f"flat K = {K}: reference {f} out of range"
+    for f, e in errs.items():
+        assert e <= SELF_TOL, f"flat K = {K}: the oracle's two flavours differ in {f} by {e:.3e} (bar {SELF_TOL:.0e})"
+    assert bw <= SELF_BW, f"flat K = {K}: the faithful loop's loading backward error {bw:.3e} (bar {SELF_BW:.0e})"
+    assert fwd <= SELF_TOL, f"flat K = {K}: the two flavours' Lambda differ forward by {fwd:.3e} (bar {SELF_TOL:.0e})"
+    assert condQ <= FLAT_COND, f"flat K = {K}: cond(Q_j) {condQ:.3g}: a forward bar on Lambda needs another n or seed"
+    assert xmax <= FLAT_XMAX, f"flat K = {K}: max|X| {xmax:.3g}"

@@ -8,6 +8,11 @@
 // The chain over h is scalar: with T_h = sum_{l>=h} tau_l s_l of the incoming
 // tau, the reference's recomputed cumprod gives dot_h = F_h T_h where
 // F_h = prod_{h'<h} delta_new(h')/delta_old(h')  (exact; rounding-level only).
+//   P == 1 (Q14): mat of dc:156 is 1 x K, so MATLAB's sum(mat(:,h:end)) runs along the row and
+//           returns the scalar sum_{l>=h} s_l; dc:157 / dc:161 then use
+//           (sum_{l>=h} tau_l)(sum_{l>=h} s_l).  The recomputed cumprod scales every tau_l, l >= h,
+//           by the same F_h, so T_h = (suffix sum of the incoming tau)_h (suffix sum of s)_h and
+//           the chain is the same.  K == 1 is unaffected (one term).
 // Every rank runs every shard's chain (delta / tau are replicated); Plam = psi o tau' (dc:175-177)
 // is formed where it is read, in the next loading-row kernel.
 #pragma once
@@ -137,6 +142,24 @@ __device__ __forceinline__ void delta_chain(const Dims &d, int l, const double (
     }
 }
 
+// P == 1 (Q14): T_h = (sum_{l>=h} tau_l)(sum_{l>=h} s_l) of shard m's incoming tau and column sums
+template <int KW, int NV>
+__device__ __forceinline__ void rate_sums_p1(const Dims &d, const double *__restrict__ sall,
+                                             const double *__restrict__ tau_in, int m, int l, double (&T)[NV]) {
+    double ts[NV], ss[NV];
+#pragma unroll
+    for (int s = 0; s < NV; ++s) {
+        const int idx = l + 64 * s, ik = idx < KW ? idx : 0;
+        const bool act = idx < d.K;
+        ts[s] = act ? tau_in[(size_t)m * KW + ik] : 0.0;
+        ss[s] = act ? sall[sall_off(d, m, KW) + ik] : 0.0;
+    }
+    suffix_sum_nv<NV>(ts, l);
+    suffix_sum_nv<NV>(ss, l);
+#pragma unroll
+    for (int s = 0; s < NV; ++s) T[s] = ts[s] * ss[s];
+}
+
 // one wave = one global shard m, lane t (< 64 active); delta / tau rows of KW, NV = KW / 64
 // (at least 1) indices per lane.  sall holds the column sums of the iteration the chain
 // updates, left by an earlier launch.
@@ -159,7 +182,8 @@ __device__ __forceinline__ void delta_shard(const Dims &d, const double *__restr
                 G0[s] = act ? delta_G(d, dr, iter, 0, idx) : 1.0;
                 id0[s] = 1.0 / d0[s];
             }
-            suffix_sum_nv<NV>(T0, l);
+            if (d.P == 1) rate_sums_p1<KW, NV>(d, sall, tau_in, 0, l, T0);   // Q14
+            else suffix_sum_nv<NV>(T0, l);
             delta_chain<NV>(d, l, T0, G0, id0, id0, d0new);   // shard 1 (index 0), its own pre-update delta_h
             double dm[NV];
 #pragma unroll
@@ -177,7 +201,8 @@ __device__ __forceinline__ void delta_shard(const Dims &d, const double *__restr
                     idold[s] = 1.0 / dold;
                     idref[s] = (idx == 0) ? idold[s] : 1.0 / d0new[s];   // delta(1,:,m) | delta(h) (Q4)
                 }
-                suffix_sum_nv<NV>(Tm, l);
+                if (d.P == 1) rate_sums_p1<KW, NV>(d, sall, tau_in, m, l, Tm);   // Q14
+                else suffix_sum_nv<NV>(Tm, l);
                 delta_chain<NV>(d, l, Tm, Gm, idold, idref, dm);
             }
             double tm[NV];

@@ -27,12 +27,20 @@ from .diagnostics import waic as _waic, conditional_log_density as _cond_ld
 from .sampler import Hyper, Sampler, count_nonzero_columns
 
 
+def _require_two_rows(n):
+    """dc:57: with n = 1 MATLAB's mean / var of the 1 x P x g array reduce along P, not along the rows, and the
+    1/(n - 1) variance of the column-wise restatement (and of k_colstats) divides by zero."""
+    if n < 2:
+        raise ValueError(f"n = {n}: at least 2 rows are needed (dc:57 mean/var reduce along P when n = 1)")
+
+
 def preprocess(Y, g, k):
     """dc:29-41. Returns (Y_kept, n, p, P, K, keep)."""
     Y = np.asarray(Y, dtype=np.float64)
     if Y.ndim != 2:
         raise ValueError("Y must be n x p (rows are observations, dc:30)")
     n, p = Y.shape
+    _require_two_rows(n)
     keep = np.flatnonzero(np.count_nonzero(Y, axis=0) != 0)     # dc:31-38
     Y = Y[:, keep]
     p = keep.size                                                # dc:39
@@ -49,6 +57,7 @@ def preprocess_device(Y, g, k, device=0):
     if Y.ndim != 2:
         raise ValueError("Y must be n x p (rows are observations, dc:30)")
     n = Y.shape[0]
+    _require_two_rows(n)
     keep = np.flatnonzero(count_nonzero_columns(Y, device=device) != 0)    # dc:31-38
     p = keep.size                                                          # dc:39
     if g < 1 or p % g or k % g:

@@ -103,7 +103,11 @@ typedef struct dcfm_handle dcfm_handle;
  * dc:62-65 (hyper-parameters), plus build-side placement and RNG settings. */
 typedef struct {
     int32_t n;          /* observations (rows of Y), dc:30                       */
-    int32_t P;          /* variables per shard, P = p/g, dc:41                   */
+    int32_t P;          /* variables per shard, P = p/g, dc:41.  P = 1 is
+                         * supported with the reference's semantics: dc:156's
+                         * mat is then 1 x K and MATLAB's sum runs along it, so
+                         * dc:157 / dc:161 use (sum tau_l)(sum s_l) over l >= h
+                         * (csrc/delta.h, quirk Q14)                              */
     int32_t g;          /* total number of shards (groups), dc:1                 */
     int32_t K;          /* factors per shard, K = k/g, dc:41                     */
     double  rho;        /* correlation of the shared factor, dc:1                */

@@ -99,14 +99,33 @@ def matlab_cumprod_delta(delta: np.ndarray) -> np.ndarray:
     return delta.copy()
 
 
+def matlab_delta_rate_sums(tau: np.ndarray, colsum: np.ndarray, P: int, h: int) -> float:
+    """``sum(tauh(h:end,:,m) .* sum(mat(:,h:end))')`` of dc:157 (h = 0) and dc:161, quirk Q14.
+
+    ``mat`` (dc:156) is P x K.  With P >= 2 MATLAB's ``sum`` runs down the rows and returns the
+    column sums, so the expression is sum_{l>=h} tau_l s_l.  With P == 1 ``mat(:,h:end)`` is a row
+    vector, ``sum`` runs along it (the first non-singleton dimension) and returns the scalar
+    sum_{l>=h} s_l; the outer sum is then (sum_{l>=h} tau_l) (sum_{l>=h} s_l).  ``colsum`` holds
+    s_l = sum_j mat(j,l), which at P == 1 is mat itself.
+    """
+    if P == 1:
+        return np.sum(tau[h:]) * np.sum(colsum[h:])
+    return np.sum(tau[h:] * colsum[h:])
+
+
 # ---------------------------------------------------------------------------
 # Driver half (dc:29-87) — stays on the host in the product as well
 # ---------------------------------------------------------------------------
 
 def preprocess(Y: np.ndarray, g: int, k: int):
-    """dc:29-42: drop all-zero columns; P = p/g, K = k/g must be integral."""
+    """dc:29-42: drop all-zero columns; P = p/g, K = k/g must be integral.
+
+    n < 2 is rejected: dc:57's ``mean`` / ``var`` of a 1 x P x g array reduce along P, not along the
+    (singleton) row dimension, which the restatement's 1/(n - 1) variance does not reproduce."""
     Y = np.asarray(Y, dtype=np.float64)
     n, p = Y.shape                                   # dc:30
+    if n < 2:
+        raise ValueError(f"n = {n}: at least 2 rows are needed (dc:57 mean/var reduce along P when n = 1)")
     nnzcol = np.count_nonzero(Y, axis=0)             # dc:31-34
     keep = np.flatnonzero(nnzcol != 0)               # dc:36,38 setdiff(1:p, zerocol)
     Y = Y[:, keep]
@@ -241,18 +260,20 @@ def update_psi(st: SamplerState, hyper: Hyper, d: IterDraws):
 
 
 def update_delta_tau(st: SamplerState, hyper: Hyper, d: IterDraws):
-    """dc:154-165 with quirks Q4 (``delta(h)`` = shard 1's delta_h) and Q5 (cumprod dim)."""
+    """dc:154-165 with quirks Q4 (``delta(h)`` = shard 1's delta_h), Q5 (cumprod dim) and Q14
+    (``sum`` of the 1 x K ``mat`` at P == 1)."""
     P, K, g = st.Lambda.shape
     delta, tauh = st.delta, st.tauh
     for m in range(g):                                             # dc:155
         mat = st.psi[:, :, m] * st.Lambda[:, :, m] ** 2            # dc:156
         colsum = mat.sum(axis=0)
-        bd = hyper.bd1 + (0.5 * (1.0 / delta[0, 0, m])) * np.sum(tauh[:, 0, m] * colsum)  # dc:157
+        bd = hyper.bd1 + (0.5 * (1.0 / delta[0, 0, m])) * matlab_delta_rate_sums(     # dc:157 (Q14)
+            tauh[:, 0, m], colsum, P, 0)
         delta[0, 0, m] = (1.0 / bd) * d.Gdelta[0, m]               # dc:158 gamrnd(ad,1/bd)
         tauh[...] = matlab_cumprod_delta(delta)                    # dc:158 (Q5)
         for h in range(1, K):                                      # dc:160
-            bd = hyper.bd2 + (0.5 * (1.0 / delta[h, 0, 0])) * np.sum(   # dc:161 delta(h) (Q4)
-                tauh[h:, 0, m] * colsum[h:])
+            bd = hyper.bd2 + (0.5 * (1.0 / delta[h, 0, 0])) * matlab_delta_rate_sums(   # dc:161 delta(h) (Q4, Q14)
+                tauh[:, 0, m], colsum, P, h)
             delta[h, 0, m] = (1.0 / bd) * d.Gdelta[h, m]           # dc:163
             tauh[:, :, m] = np.cumprod(delta[:, :, m], axis=0)     # dc:163
 

@@ -23,7 +23,7 @@ from __future__ import annotations
 import numpy as np
 from scipy.linalg.blas import dsyrk, dtrsv
 
-from .dc_oracle import Hyper, SamplerState, matlab_cumprod_delta
+from .dc_oracle import Hyper, SamplerState, matlab_cumprod_delta, matlab_delta_rate_sums
 from .draws import IterDraws
 
 
@@ -156,17 +156,17 @@ def update_Lambda_psi_delta_ps(st: SamplerState, D: Data, hyper: Hyper, d: IterD
 
 
 def update_delta_tau(st: SamplerState, hyper: Hyper, d: IterDraws):
-    """dc:154-165: sequential scalar chain, kept as in the faithful loop (Q4, Q5)."""
+    """dc:154-165: sequential scalar chain, kept as in the faithful loop (Q4, Q5, Q14)."""
     P, K, g = st.Lambda.shape
     colsum = (st.psi * st.Lambda ** 2).sum(axis=0)                   # K x g
     delta, tauh = st.delta, st.tauh
     for m in range(g):
         cs = colsum[:, m]
-        bd = hyper.bd1 + (0.5 * (1.0 / delta[0, 0, m])) * np.sum(tauh[:, 0, m] * cs)
+        bd = hyper.bd1 + (0.5 * (1.0 / delta[0, 0, m])) * matlab_delta_rate_sums(tauh[:, 0, m], cs, P, 0)
         delta[0, 0, m] = (1.0 / bd) * d.Gdelta[0, m]
         tauh[...] = matlab_cumprod_delta(delta)
         for h in range(1, K):
-            bd = hyper.bd2 + (0.5 * (1.0 / delta[h, 0, 0])) * np.sum(tauh[h:, 0, m] * cs[h:])
+            bd = hyper.bd2 + (0.5 * (1.0 / delta[h, 0, 0])) * matlab_delta_rate_sums(tauh[:, 0, m], cs, P, h)
             delta[h, 0, m] = (1.0 / bd) * d.Gdelta[h, m]
             tauh[:, :, m] = np.cumprod(delta[:, :, m], axis=0)
 

@@ -6,6 +6,9 @@ state), the injected standard variates for every iteration, the state after
 every iteration and the final Sigmaout.  Cases follow SURVEY.md §4.2:
   (i) K >= 2, g >= 3 (quirk Q4)      (ii) K = 1, g >= 3 (quirk Q5)
   (iii) thin does not divide BURNIN  (iv) zero columns (dc:31-39)   (v) g = 1
+  (vi) P = 1, K >= 2, g >= 3 (quirk Q14 beside Q4: MATLAB's sum of the 1 x K mat)
+With case names as arguments only those are written (a committed fixture is never
+regenerated for a change that does not move it):  python tests/golden/make_golden.py case_vi_P1_K2_g3
 These fixtures pin the HIP kernels (and the oracle against regressions); they
 do not pin MATLAB — parity against the reference itself is unpinned (no
 MATLAB/Octave, no reference fixtures; see oracle/__init__.py).
@@ -32,6 +35,7 @@ CASES = {
     "case_iii_thin2_burnin1": (10, 16, 4, 2, 1, 2, 2, 0, 103),
     "case_iv_zero_cols": (12, 20, 3, 2, 0, 3, 1, 2, 104),
     "case_v_g1": (10, 5, 1, 2, 0, 3, 1, 0, 105),
+    "case_vi_P1_K2_g3": (9, 3, 3, 2, 1, 2, 1, 0, 106),
 }
 
 
@@ -64,6 +68,6 @@ def make(name, n, p_raw, g, K, burnin, mcmc, thin, zero_cols, seed):
 
 
 if __name__ == "__main__":
-    for name, args in CASES.items():
-        p = make(name, *args)
+    for name in sys.argv[1:] or CASES:
+        p = make(name, *CASES[name])
         print(p.name, p.stat().st_size, "bytes")

@@ -64,14 +64,17 @@ def _plan(flat):
 
 
 @functools.lru_cache(maxsize=None)
-def _run(dcfm, K, mode, flat=False):
+def _run(dcfm, K, mode, flat=False, cases=kp):
     """The chain of case K in `mode`, one iteration per call: the states (the start first), Sigmaout and the
-    saved-sample count.  Made once, shared, read only.  `flat`: k_paths.flat_case, exactly one iteration."""
-    c = kp.flat_case(K) if flat else kp.case(K)
-    n, P, g, _ = kp.shape(K)
+    saved-sample count.  Made once, shared, read only.  `flat`: k_paths.flat_case, exactly one iteration.
+    `cases`: the case list's module (case, shape, case_id, MODES and the same 3-iteration plan): k_paths, keyed by
+    K, or tests/tiny_shapes.py, keyed by (n, P, g, K)."""
+    c = cases.flat_case(K) if flat else cases.case(K)
+    n, P, g, Kf = cases.shape(K)
     burnin, mcmc, thin, n_iter = _plan(flat)
+    assert flat or (cases.BURNIN, cases.MCMC, cases.THIN, cases.N_ITER) == (burnin, mcmc, thin, n_iter)
     start = state_dict(c["st"])
-    smp = dcfm.Sampler(n, P, g, K, c["rho"], burnin, mcmc, thin, inject_draws=True, flags=kp.MODES[mode])
+    smp = dcfm.Sampler(n, P, g, Kf, c["rho"], burnin, mcmc, thin, inject_draws=True, flags=cases.MODES[mode])
     try:
         smp.set_data(c["Yd"])
         smp.set_state({f: v for f, v in start.items() if f != "eta"})
@@ -90,11 +93,11 @@ def _run(dcfm, K, mode, flat=False):
     return out
 
 
-def _check(dcfm, K, mode, flat=False):
-    c = kp.flat_case(K) if flat else kp.case(K)
-    r = _run(dcfm, K, mode, flat)
+def _check(dcfm, K, mode, flat=False, cases=kp):
+    c = cases.flat_case(K) if flat else cases.case(K)
+    r = _run(dcfm, K, mode, flat, cases)
     burnin, mcmc, thin, n_iter = _plan(flat)
-    tag = "K_PATHS_FLAT" if flat else "K_PATHS"
+    tag = ("K_PATHS_FLAT" if flat else "K_PATHS") if cases is kp else "TINY_SHAPES"
     states = r["states"]
     assert len(states) == n_iter + 1
     worst = {}
@@ -118,7 +121,7 @@ def _check(dcfm, K, mode, flat=False):
         worst["lambda_sbw_over_bar"] = max(worst.get("lambda_sbw_over_bar", 0.0), float(sbw[at] / bars[at]))
         worst["lambda_sbw_well"] = max(worst.get("lambda_sbw_well", 0.0), float(sbw[well].max()) if well.any() else 0.0)
         worst["cond_dqd"] = max(worst.get("cond_dqd", 0.0), float(cond.max()))
-        print(f"{tag} {kp.case_id(K)} {mode} iter {it}:", {f: f"{e:.2e}" for f, e in sorted(errs.items())},
+        print(f"{tag} {cases.case_id(K)} {mode} iter {it}:", {f: f"{e:.2e}" for f, e in sorted(errs.items())},
               f"lambda_bw {bw:.2e} lambda_sbw {sbw.max():.2e} (worst against its bar: {sbw[at]:.2e} at shard {at[0]} row "
               f"{at[1]}, cond(DQD) {cond[at]:.2e}, bar {bars[at]:.0e}; {int((~well).sum())} of {well.size} rows over "
               f"cond 1e3, cond(DQD) <= {cond.max():.2e})")
@@ -131,7 +134,7 @@ def _check(dcfm, K, mode, flat=False):
             # cond(Q_j) <= 310 here, so a forward bar on Lambda is legitimate: the oracle's draw from got's own eta
             fwd = rel_err(got["Lambda"], _oracle_lambda(states[it - 1], got, c, it))
             worst["lambda_fwd"] = fwd
-            print(f"{tag} {kp.case_id(K)} {mode}: Lambda forward {fwd:.2e}")
+            print(f"{tag} {cases.case_id(K)} {mode}: Lambda forward {fwd:.2e}")
             assert fwd <= FLAT_FWD_TOL, f"flat K = {K} {mode}: Lambda against the oracle's {fwd:.3e} (bar {FLAT_FWD_TOL:.0e})"
     # Sigmaout (dc:180-195) from the device's own saved states
     S = r["sigma"]
@@ -140,7 +143,7 @@ def _check(dcfm, K, mode, flat=False):
     saved = [it for it in range(1, n_iter + 1) if it % thin == 0 and it > burnin]
     want = sum(F.assemble_sample(as_oracle_state(states[it]), c["rho"]) for it in saved) / (mcmc / thin)
     worst["sigma"] = float(np.max(np.abs(S - want)) / np.max(np.abs(want)))
-    print(f"{tag}_WORST {kp.case_id(K)} {mode} classes {kp.classes(K)} shape {kp.shape(K)}:",
+    print(f"{tag}_WORST {cases.case_id(K)} {mode} classes {kp.classes(cases.shape(K)[3])} shape {cases.shape(K)}:",
           {f: f"{e:.2e}" for f, e in sorted(worst.items())})
     assert worst["sigma"] < SIGMA_TOL, f"K = {K} {mode}: Sigmaout vs the device's own samples {worst['sigma']:.3e}"
     return worst

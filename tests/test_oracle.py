@@ -116,7 +116,78 @@ def test_delta_chain_reads_shard1_delta_quirk_Q4():
     assert np.isclose(a.delta[1, 0, 1], (1 / bd) * d.Gdelta[1, 1], rtol=1e-13)
 
 
-@pytest.mark.parametrize("n,p,g,K", [(20, 24, 3, 2), (20, 24, 3, 1), (15, 12, 1, 3), (30, 40, 4, 5)])
+def test_delta_rate_sums_first_nonsingleton_dim_quirk_Q14():
+    """dc:157 / dc:161: sum(mat(:,h:end)) of the P x K mat is the column sums for P >= 2 and one scalar for P = 1."""
+    r = np.random.default_rng(6)
+    tau, s = r.uniform(0.5, 2, 5), r.uniform(0.5, 2, 5)
+    for h in range(5):
+        assert F.matlab_delta_rate_sums(tau, s, 4, h) == np.sum(tau[h:] * s[h:])
+        assert F.matlab_delta_rate_sums(tau, s, 1, h) == np.sum(tau[h:]) * np.sum(s[h:])
+    assert F.matlab_delta_rate_sums(tau, s, 1, 4) == tau[4] * s[4]          # one term left: the two readings meet
+
+
+def test_golden_P1_delta_rate_by_hand_quirk_Q14():
+    """tests/golden/case_vi_P1_K2_g3.npz (P = 1, K = 2, g = 3): iteration 2's delta step of shard 2, recomputed in
+    plain Python floats from the state before it.  With P = 1 dc:156's mat is 1 x 2 and MATLAB's sum runs along it:
+      h = 1:  bd = bd1 + 0.5 / delta_{1,m} (tau_1 + tau_2)(s_1 + s_2)                      dc:157
+      h = 2:  bd = bd2 + 0.5 / delta_2(shard 1, updated) tau'_2 s_2,  tau' = cumprod      dc:158, 161 (Q4)
+    Both oracle flavours must give G / bd within 1e-14 and the fixture holds it; the per-column reading
+    (tau_1 s_1 + tau_2 s_2) must miss bd of h = 1 by more than 1e-3, so the fixture cannot pass under it."""
+    from pathlib import Path
+    from test_golden import draws_fn, load, STATE
+    fx = load(Path(__file__).parent / "golden" / "case_vi_P1_K2_g3.npz")
+    n, p, g, K, burnin, mcmc, thin, seed = (int(v) for v in fx["meta"])
+    assert (p // g, K, g) == (1, 2, 3)
+    hyper, rho, it, m = F.Hyper(), float(fx["rho"]), 2, 1
+    dr = draws_fn(fx)(it)
+    st = F.SamplerState(**{f: fx[f"it{it - 1}_{f}"].copy() for f in STATE})
+    F.update_Z(st, fx["Yd"], rho, dr)
+    F.update_X(st, fx["Yd"], rho, dr)
+    F.update_eta(st, rho)
+    F.update_Lambda(st, fx["Yd"], dr)
+    F.update_psi(st, hyper, dr)                      # the state before the delta step
+
+    def hand(mm, d2_ref):
+        """(bd of h = 1, bd of h = 2, new delta_1, new delta_2) of shard mm; d2_ref: dc:161's delta(h), None = own."""
+        s1, s2 = (float(st.psi[0, k, mm]) * float(st.Lambda[0, k, mm]) ** 2 for k in range(2))
+        d1, d2 = float(st.delta[0, 0, mm]), float(st.delta[1, 0, mm])
+        t1, t2 = float(st.tauh[0, 0, mm]), float(st.tauh[1, 0, mm])
+        bd_1 = hyper.bd1 + 0.5 / d1 * ((t1 + t2) * (s1 + s2))
+        bd_1_percol = hyper.bd1 + 0.5 / d1 * (t1 * s1 + t2 * s2)
+        d1n = float(dr.Gdelta[0, mm]) / bd_1
+        t2n = d1n * d2                               # dc:158 cumprod
+        bd_2 = hyper.bd2 + 0.5 / (d2 if d2_ref is None else d2_ref) * (t2n * s2)
+        return bd_1, bd_2, d1n, float(dr.Gdelta[1, mm]) / bd_2, bd_1_percol
+
+    _, _, _, d2_shard1, _ = hand(0, None)            # shard 1's own chain first: its updated delta_2 (Q4)
+    bd_1, bd_2, d1n, d2n, bd_1_percol = hand(m, d2_shard1)
+    assert abs(bd_1_percol - bd_1) > 1e-3 * bd_1, "the fixture does not tell the two readings of sum(mat) apart"
+    for name, mod in (("faithful", F), ("vectorised", V)):
+        a = st.copy()
+        mod.update_delta_tau(a, hyper, dr)
+        for h, (bd, dn) in enumerate(((bd_1, d1n), (bd_2, d2n))):
+            got_bd = float(dr.Gdelta[h, m]) / float(a.delta[h, 0, m])
+            assert abs(got_bd - bd) <= 1e-14 * bd, (name, h, got_bd, bd)
+            assert abs(float(a.delta[h, 0, m]) - dn) <= 1e-14 * dn, (name, h)
+        assert abs(float(a.tauh[1, 0, m]) - d1n * d2n) <= 1e-14 * d1n * d2n, name
+    assert abs(float(fx[f"it{it}_delta"][0, 0, m]) - d1n) <= 1e-14 * d1n
+    assert abs(float(fx[f"it{it}_delta"][1, 0, m]) - d2n) <= 1e-14 * d2n
+
+
+def test_preprocess_rejects_one_row():
+    """dc:57: mean / var of a 1 x P x g array reduce along P; the column-wise restatement would divide by n - 1 = 0.
+    The oracle's preprocess and the driver's host path raise a ValueError that cites dc:57 (the device path:
+    tests/test_gpu_tiny_shapes.py)."""
+    import __graft_entry__ as ge
+    dcfm = ge.load_package()
+    Y = np.arange(1.0, 7.0)[None, :]
+    for fn in (F.preprocess, dcfm.preprocess):
+        with pytest.raises(ValueError, match="dc:57"):
+            fn(Y, 3, 3)
+        assert fn(np.vstack([Y, Y + 1.0]), 3, 3)[1:3] == (2, 6)      # n = 2 is accepted
+
+
+@pytest.mark.parametrize("n,p,g,K", [(20, 24, 3, 2), (20, 24, 3, 1), (15, 12, 1, 3), (30, 40, 4, 5), (9, 3, 3, 2)])
 def test_faithful_vs_vectorised(n, p, g, K):
     c = make_case(n, p, g, K, seed=9)
     s1, s2 = c["st"].copy(), c["st"].copy()

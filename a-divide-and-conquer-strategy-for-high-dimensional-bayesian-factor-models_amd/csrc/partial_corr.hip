@@ -25,10 +25,10 @@
 // 1 - rounding).  A sum of such terms over several flushes can still round (0.4 + 0.4 + 0.4 != 3 / 2.5), so the
 // read-out writes the diagonal from the handle's own count: saved / effsamp for both moments, 0 for the standard
 // deviation (sigma_out.hip, k_sigma_pack's dset).
-#include "dcfm_internal.h"
-#include "linalg.h"
+#include "slot_tiles.h"
 
 namespace dcfm {
+using namespace slot;
 
 constexpr int PCS_LANES = 16;      // lanes of a (row, slot) group of k_pc_scale: 16 groups per block, 4 per wave
 
@@ -53,140 +53,49 @@ __global__ __launch_bounds__(256) void k_pc_scale(double *Fb, int KH, const doub
         for (int h = 0; h < 4; ++h) F[h * (size_t)KH + k] *= sc;
 }
 
-// ============================================================================
-// k_assemble_pc_m2: k_assemble_m2's tile list, XCD remap, block-sharding, wave tile (8 waves, each 32 x 64:
-// 64 product and 64 square accumulator VGPRs) and tile-packed layout, into PC2.  The operands are two distinct
-// panels of the scaled factor buffer: the tile's rows from the Left quarters, its columns from the Right ones.
-// A slot runs nph = 1 + ncommon phases of nch chunks: phase 0 the G quarters, phase 1 + i the A quarters with
-// every row of both panels outside shard sig0 + i staged as zero.  A slot starts at column s K of a quarter
-// (8-byte aligned only) and ends inside a k-step unless 4 | K: staging is predicated on k < K, as in k_assemble_m2.
-// After the slot's last chunk t = the product, 1 on the diagonal, acc2 = fma(t, t, acc2), the product restarts.
-// ============================================================================
-constexpr int CKC = ASM_KC, CLD = ASM_TILE + 16, PC2_THREADS = 512;
-
-__global__ __launch_bounds__(PC2_THREADS) void k_assemble_pc_m2(Dims d, const double *__restrict__ Fb, int KH,
-                                                                int nslots, double inv_eff,
-                                                                const int2 *__restrict__ tiles, int T0,
-                                                                double *__restrict__ PC2) {
-    __shared__ double As[2][CKC][CLD], Bs[2][CKC][CLD];
-    const int2 T = tiles[xcd_remap(blockIdx.x, gridDim.x)];
-    double *__restrict__ St = PC2 + (size_t)(tri(T.x) - tri(T0) + T.y) * ASM_TILE * ASM_TILE;
-    const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
-    const int r = lane & 15, q = lane >> 4;
+// k_assemble_pc_m2: the per-slot tile loop of slot_tiles.h into PC2.  Its own: the operands are two distinct panels
+// of the scaled factor buffer, the tile's rows from the Left quarters, its columns from the Right ones; a slot runs
+// nph = 1 + ncommon phases: phase 0 the G quarters, phase 1 + i the A quarters with every row of both panels outside
+// shard sig0 + i staged as zero; the fold takes 1 on the diagonal.
+__global__ __launch_bounds__(THREADS) void k_assemble_pc_m2(Dims d, const double *__restrict__ Fb, int KH, int nslots,
+                                                            double inv_eff, const int2 *__restrict__ tiles, int T0,
+                                                            double *__restrict__ PC2) {
+    __shared__ Panel As, Bs;
+    const Tile g(d, tiles, T0);
+    const Rows R(g, d);
     const int p = d.p, K = d.K;
-    const size_t LDF = 4 * (size_t)KH;
-    const int w4 = wave >> 1, u0 = 2 * (wave & 1);           // k_assemble's wave and first 16-row tile
-    const int wa = (w4 >> 1) * 64 + 16 * u0, wb = (w4 & 1) * 64;
     // the rows' shards are sig0 .. and the columns' end at clast / P <= the rows' last (T.y <= T.x): the
     // shards present on both sides are sig0 .. clast / P (none on a pure cross-shard tile)
-    const int clast = min(p, T.y * ASM_TILE + ASM_TILE) - 1;
-    const int sig0 = (T.x * ASM_TILE) / d.P;
-    const int nph = 1 + max(0, clast / d.P - sig0 + 1);
-    const bool diag = T.x == T.y;
-    // global -> LDS as k_assemble_m2: value i of thread t is column (t & 7) + 8 (i & 1) of row
-    // (t >> 3) + 64 (i >> 1) of [row panel | column panel]
-    const int k8 = t & 7, rsub = t >> 3;
+    const int sig0 = (g.T.x * ASM_TILE) / d.P;
+    const int nph = 1 + max(0, g.clast / d.P - sig0 + 1);
     const double *prow[4];
-    bool vrow[4];
-    int shr[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int grow = (j < 2 ? T.x : T.y) * ASM_TILE + ((rsub + 64 * j) & 127);
-        vrow[j] = grow < p;
-        shr[j] = grow / d.P;
-        prow[j] = Fb + (size_t)(vrow[j] ? grow : 0) * LDF + (j < 2 ? 0 : 2 * (size_t)KH) + k8;
-    }
-    const int K4 = (K + 3) & ~3, nch = (K4 + CKC - 1) / CKC, total = nslots * nph * nch;
+    R.pointers(prow, Fb, Fb + 2 * (size_t)KH, 4 * (size_t)KH);
     double rg[8];
-    auto gload = [&](int s, int ph, int c) {   // chunk c of phase ph of slot s: columns s*K + 16 c + [0, 16), those < K
-        const size_t col = (ph ? (size_t)KH : 0) + (size_t)s * K + CKC * c;
-        const int kleft = K - CKC * c - k8;    // this thread's columns k8, k8 + 8 are valid if > 0, > 8
+    auto gload = [&](int s, int ph, int c) {   // columns s*K + 16 c + [0, 16) of the phase's quarters, those < K
+        const size_t col = (ph ? (size_t)KH : 0) + (size_t)s * K + KC * c;
         const int sig = sig0 + ph - 1;
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-            const bool ok = vrow[i >> 1] && 8 * (i & 1) < kleft && (ph == 0 || shr[i >> 1] == sig);
+            const bool ok = R.has(i, c, K) && (ph == 0 || R.shard[i >> 1] == sig);
             rg[i] = ok ? prow[i >> 1][col + 8 * (i & 1)] : 0.0;
         }
     };
-    auto lstore = [&](int buf) {
+    auto lstore = [&](int buf, int) {
 #pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int k = k8 + 8 * (i & 1), row = (rsub + 64 * (i >> 1)) & 127;
-            if (i < 4) As[buf][k][row] = rg[i];
-            else Bs[buf][k][row] = rg[i];
-        }
+        for (int i = 0; i < 8; ++i) (i < 4 ? As : Bs)[buf][R.k(i)][R.row(i)] = rg[i];
     };
-    d4 acc[2][4], acc2[2][4];
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int v = 0; v < 4; ++v) acc[u][v] = acc2[u][v] = d4{0.0, 0.0, 0.0, 0.0};
-    if (total > 0) {
-        gload(0, 0, 0);
-        lstore(0);
-    }
-    __syncthreads();
-    const int a0 = T.x * ASM_TILE + wa, b0 = T.y * ASM_TILE + wb;
-    for (int i = 0, s = 0, ph = 0, c = 0, buf = 0; i < total; ++i, buf ^= 1) {
-        const bool more = i + 1 < total;
-        const bool last_chunk = c == nch - 1, last_phase = ph == nph - 1;
-        const int cn = last_chunk ? 0 : c + 1;
-        const int phn = last_chunk ? (last_phase ? 0 : ph + 1) : ph;
-        const int sn = (last_chunk && last_phase) ? s + 1 : s;
-        if (more) gload(sn, phn, cn);
-        const int nk4 = min(CKC, K4 - CKC * c);   // k extent of this chunk (a multiple of 4)
-#pragma unroll
-        for (int s4 = 0; s4 < CKC / 4; ++s4) {
-            if (4 * s4 >= nk4) break;            // block-uniform
-            double a[2], b[4];
-#pragma unroll
-            for (int u = 0; u < 2; ++u) a[u] = As[buf][4 * s4 + q][wa + 16 * u + r];
-#pragma unroll
-            for (int v = 0; v < 4; ++v) b[v] = Bs[buf][4 * s4 + q][wb + 16 * v + r];
-#pragma unroll
-            for (int u = 0; u < 2; ++u)
-#pragma unroll
-                for (int v = 0; v < 4; ++v) acc[u][v] = mfma16x16x4(a[u], b[v], acc[u][v]);
-        }
-        if (last_chunk && last_phase) {   // the slot's R(s) tile is complete: square it into acc2, restart the product
-#pragma unroll
-            for (int u = 0; u < 2; ++u)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int a = a0 + 16 * u + q + 4 * g;
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) {
-                        const int b = b0 + 16 * v + r;
-                        const double tv = (diag && a == b) ? 1.0 : acc[u][v][g];
-                        acc2[u][v][g] = fma(tv, tv, acc2[u][v][g]);
-                    }
-                }
-#pragma unroll
-            for (int u = 0; u < 2; ++u)
-#pragma unroll
-                for (int v = 0; v < 4; ++v) acc[u][v] = d4{0.0, 0.0, 0.0, 0.0};
-        }
-        if (more) lstore(buf ^ 1);
-        __syncthreads();
-        s = sn;
-        ph = phn;
-        c = cn;
-    }
-    // epilogue: PC2 tile += acc2 / effsamp, the wave's (u, v, h) slices as 16-byte accesses; the strict upper
-    // part of a diagonal tile and the rows past p stay zero (as in Sigma)
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int v = 0; v < 4; ++v)
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                d2 *ptr = reinterpret_cast<d2 *>(St + sig_tile_off(u0 + u, v, 2 * h, w4, lane));
-                const int b = b0 + 16 * v + r, a = a0 + 16 * u + q + 8 * h;
-                d2 o = __builtin_nontemporal_load(ptr);
-                o.x += (a < p && b <= a) ? inv_eff * acc2[u][v][2 * h] : 0.0;
-                o.y += (a + 4 < p && b <= a + 4) ? inv_eff * acc2[u][v][2 * h + 1] : 0.0;
-                __builtin_nontemporal_store(o, ptr);
-            }
+    d4 acc2[2][4];
+    zero(acc2);
+    auto fold = [&](int, const d4 (&acc)[2][4]) {
+        each([&](int u, int v, int e) {
+            const int a = g.a0() + 16 * u + g.q + 4 * e, b = g.b0() + 16 * v + g.r;
+            const double tv = (g.diag && a == b) ? 1.0 : acc[u][v][e];
+            acc2[u][v][e] = fma(tv, tv, acc2[u][v][e]);
+        });
+    };
+    auto none = [](int, int, int) {};
+    loop<0>(g, As, Bs, K, nslots, nph, gload, lstore, none, none, fold);
+    add_tile(g, PC2 + g.off, p, inv_eff, acc2);
 }
 
 void launch_partial_corr(const Dims &d, const Bufs &b, const PrecMean &pm, const PartialCorr &pc, const double *wslot,
@@ -198,7 +107,7 @@ void launch_partial_corr(const Dims &d, const Bufs &b, const PrecMean &pm, const
                        d.p, d.K, nslots);
     launch_pc_mean(d, b, pm, nslots, inv_eff, pc.PC, s);
     if (b.ntiles == 0) return;
-    hipLaunchKernelGGL(k_assemble_pc_m2, dim3(b.ntiles), dim3(PC2_THREADS), 0, s, d, pm.pfac, pm.KH, nslots, inv_eff,
+    hipLaunchKernelGGL(k_assemble_pc_m2, dim3(b.ntiles), dim3(THREADS), 0, s, d, pm.pfac, pm.KH, nslots, inv_eff,
                        b.tiles, b.T0, pc.PC2);
 }
 

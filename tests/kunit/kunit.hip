@@ -1,5 +1,5 @@
 // Test-only device library: one small __global__ wrapper per device primitive of csrc/linalg.h,
-// csrc/tile_linalg.h, csrc/delta.h and csrc/gj.h, so that tests/test_gpu_kunit_*.py can feed each routine
+// csrc/tile_linalg.h, csrc/delta.h, csrc/gj.h and csrc/slot_tiles.h, so that tests/test_gpu_kunit_*.py can feed each routine
 // inputs of their own choosing (tests/kunit_ref.py) instead of the matrices a chain happens to produce.
 // The product headers are included unchanged.  Every wrapper stages its operands the way the product caller
 // does, calls the routine and stores what it left; block sizes and LDS layouts are the callers'.  One launch
@@ -15,6 +15,7 @@
 #include "tile_linalg.h"
 #include "delta.h"
 #include "gj.h"
+#include "slot_tiles.h"
 
 using namespace dcfm;
 
@@ -290,6 +291,46 @@ __global__ __launch_bounds__(64) void k_delta(const double *tt, const double *Gm
     for (int s = 0; s < NV; ++s) dnew[ro + l + 64 * s] = dn[s];
 }
 
+// ---------------------------------------------------------------- slot_tiles.h
+// The per-slot tile loop with the plainest hooks: two row-major panels A, Bm [p][2 KH] (slot s of phase ph at
+// columns ph KH + s K), phase 1 staging only the rows of shard sig, a fold that squares the product.  The grid is
+// ncase x ntile blocks over the tile list repeated per case; case e / ntile runs ns[case] slots into its own
+// tile-packed output
+__global__ __launch_bounds__(slot::THREADS) void k_slot(Dims d, const double *__restrict__ A,
+                                                        const double *__restrict__ Bm, int KH,
+                                                        const int *__restrict__ ns, int ntile, int nph, int sig,
+                                                        double inv_eff, const int2 *__restrict__ tiles,
+                                                        double *__restrict__ out) {
+    __shared__ slot::Panel As, Bs;
+    const slot::Tile g(d, tiles, 0);
+    const slot::Rows R(g, d);
+    const int cs = xcd_remap(blockIdx.x, gridDim.x) / ntile, K = d.K;
+    const double *prow[4];
+    R.pointers(prow, A, Bm, 2 * (size_t)KH);
+    double rg[8];
+    auto gload = [&](int s, int ph, int c) {
+        const size_t col = (size_t)ph * KH + (size_t)s * K + slot::KC * c;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const bool ok = R.has(i, c, K) && (ph == 0 || R.shard[i >> 1] == sig);
+            rg[i] = ok ? prow[i >> 1][col + 8 * (i & 1)] : 0.0;
+        }
+    };
+    auto lstore = [&](int buf, int) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) (i < 4 ? As : Bs)[buf][R.k(i)][R.row(i)] = rg[i];
+    };
+    d4 acc2[2][4];
+    slot::zero(acc2);
+    auto fold = [&](int, const d4 (&acc)[2][4]) {
+        slot::each([&](int u, int v, int e) { acc2[u][v][e] = fma(acc[u][v][e], acc[u][v][e], acc2[u][v][e]); });
+    };
+    auto none = [](int, int, int) {};
+    if (nph == 1) slot::loop<1>(g, As, Bs, K, ns[cs], 1, gload, lstore, none, none, fold);
+    else slot::loop<0>(g, As, Bs, K, ns[cs], nph, gload, lstore, none, none, fold);
+    slot::add_tile(g, out + (size_t)cs * ntile * ASM_TILE * ASM_TILE + g.off, d.p, inv_eff, acc2);
+}
+
 // ---------------------------------------------------------------- host side
 struct Dev {
     void *p = nullptr;
@@ -513,6 +554,32 @@ int kunit_delta(int nv, const double *tt, const double *G, const double *idold, 
                            d3.as<double>(), dk.as<int>(), bd1, bd2, dout.as<double>());
     KI(finish());
     return down(dnew, dout, nb);
+}
+
+// A, B: [p][2 KH] row-major; ns: the cases' slot counts; out: ncase tile-packed lower triangles of
+// cdiv(p, 128) tile rows (128 x 128 doubles a tile), which go up as given and come back with the sums added
+int kunit_slot(const double *A, const double *B, int p, int P, int K, int KH, const int *ns, int ncase, int nph, int sig,
+               double inv_eff, double *out) {
+    if (p <= 0 || P <= 0 || p % P || K < 1 || K > KH || ncase <= 0 || (nph != 1 && nph != 2)) return (int)hipErrorInvalidValue;
+    for (int c = 0; c < ncase; ++c)
+        if (ns[c] < 0 || (long long)ns[c] * K > KH) return (int)hipErrorInvalidValue;   // every slot inside its phase's half
+    const int nt = (p + ASM_TILE - 1) / ASM_TILE, ntile = nt * (nt + 1) / 2;
+    int2 *tl = new int2[(size_t)ncase * ntile];
+    for (int c = 0, e = 0; c < ncase; ++c)
+        for (int ti = 0; ti < nt; ++ti)
+            for (int tj = 0; tj <= ti; ++tj) tl[e++] = make_int2(ti, tj);
+    Dims d{};
+    d.p = p, d.P = P, d.g = p / P, d.K = K;
+    const size_t pb = (size_t)p * 2 * KH * 8, ob = (size_t)ncase * ntile * ASM_TILE * ASM_TILE * 8;
+    Dev da, db, dn, dt, dout;
+    int rc = up(dt, tl, (size_t)ncase * ntile * sizeof(int2));
+    delete[] tl;
+    KI(rc);
+    KI(up(da, A, pb)); KI(up(db, B, pb)); KI(up(dn, ns, (size_t)ncase * 4)); KI(up(dout, out, ob));
+    hipLaunchKernelGGL(k_slot, dim3(ncase * ntile), dim3(slot::THREADS), 0, 0, d, da.as<double>(), db.as<double>(), KH,
+                       dn.as<int>(), ntile, nph, sig, inv_eff, dt.as<int2>(), dout.as<double>());
+    KI(finish());
+    return down(out, dout, ob);
 }
 
 }  // extern "C"

@@ -426,7 +426,7 @@ def lib():
     """libdcfm_kunit.so (built by csrc/Makefile's default target); a missing library is an error."""
     L = ctypes.CDLL(str(LIB_PATH))
     for name in ("scalar", "lane_rows", "lanes", "sums", "tree", "xcd", "chol16p", "chol16blk", "chol32", "tile", "gj",
-                 "delta"):
+                 "delta", "slot"):
         getattr(L, "kunit_" + name).restype = ctypes.c_int
     return L
 

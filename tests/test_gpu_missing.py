@@ -96,11 +96,12 @@ def _open(dcfm, name, mask, *, flags=0, burnin=0, mcmc=RN, thin=1, asm_batch=0, 
     return smp
 
 
-def _stepped(dcfm, name, pattern, flags=0):
-    """NSTEP iterations, one per call: [(Y before, state before, state after, Y after)] per iteration."""
+def _stepped(dcfm, name, pattern, flags=0, mask=None):
+    """NSTEP iterations, one per call: [(Y before, state before, state after, Y after)] per iteration (`mask`: the
+    mask itself where `pattern` is not one of missing_cases.make_mask's)."""
     def run():
-        mask = _mask(name, pattern)
-        smp = _open(dcfm, name, mask, flags=flags, capacity=0)
+        mk = _mask(name, pattern) if mask is None else mask
+        smp = _open(dcfm, name, mk, flags=flags, capacity=0)
         out = []
         try:
             Y, st = smp.get_data(), smp.get_state()
@@ -119,12 +120,10 @@ def _stepped(dcfm, name, pattern, flags=0):
 STEP_CASES = [("A", p) for p in mc.PATTERNS] + [(n, p) for n in "BCD" for p in ("random", "edges")]
 
 
-@pytest.mark.parametrize("name,pattern", STEP_CASES)
-def test_the_step_is_the_conditional(dcfm, name, pattern):
-    c = _case(name)
-    mask = _mask(name, pattern)
+def _check_step(c, mask, steps, what):
+    """The step is the conditional: `steps` is _stepped's list for the case c under `mask`."""
     worst = 0.0
-    for it, (Y0, _, got, Y1) in enumerate(_stepped(dcfm, name, pattern), start=1):
+    for it, (Y0, _, got, Y1) in enumerate(steps, start=1):
         assert np.array_equal(Y1[~mask], c["Yd"][~mask]), f"iteration {it}: an observed entry moved"
         if not mask.any():
             continue
@@ -135,16 +134,20 @@ def test_the_step_is_the_conditional(dcfm, name, pattern):
         worst = max(worst, ratio)
         assert ratio <= 1.0, f"iteration {it}: a missing entry is off its conditional draw by {ratio:.3g} x the bar"
         assert not np.array_equal(Y1[mask], Y0[mask])                       # the entries were redrawn
-    print(f"MISSING_STEP {name} {pattern}: worst ratio to the 1e-12 bar {worst:.3e}")
+    print(f"MISSING_STEP {what}: worst ratio to the 1e-12 bar {worst:.3e}")
+    return worst
+
+
+@pytest.mark.parametrize("name,pattern", STEP_CASES)
+def test_the_step_is_the_conditional(dcfm, name, pattern):
+    _check_step(_case(name), _mask(name, pattern), _stepped(dcfm, name, pattern), f"{name} {pattern}")
 
 
 # ---- 2 ---------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("flags", [0, mc.EXACT_RESIDUAL, mc.GUARD_ALL], ids=["default", "exact", "guard_all"])
-@pytest.mark.parametrize("name", ["A", "C"])
-def test_the_sweep_reads_the_completed_data(dcfm, name, flags):
-    c = _case(name)
+def _check_sweep(c, steps, what):
+    """The sweep reads the completed data: iteration t of `steps` (_stepped's list) against the oracle on Y_{t-1}."""
     worst, worst_bw = {}, 0.0
-    for it, (Y0, st0, got, _) in enumerate(_stepped(dcfm, name, "random", flags), start=1):
+    for it, (Y0, st0, got, _) in enumerate(steps, start=1):
         errs, bw, _, (sbw, cond) = stagewise_errors(_as_oracle(st0), got, Y0, c["rho"], c["hyper"],
                                                     c["src"].iteration(it), scaled=True)
         for f, e in errs.items():
@@ -152,13 +155,20 @@ def test_the_sweep_reads_the_completed_data(dcfm, name, flags):
         worst_bw = max(worst_bw, bw)
         # the scaled loading measure is printed beside the normwise one, not asserted (these states have not been
         # measured against the reference: tests/test_loading_measure.py)
-        print(f"MISSING_STAGEWISE {name} flags {flags:#x} it {it}:", {k: f"{v:.2e}" for k, v in errs.items()},
+        print(f"MISSING_STAGEWISE {what} it {it}:", {k: f"{v:.2e}" for k, v in errs.items()},
               f"bw {bw:.2e} sbw {sbw.max():.2e} cond(DQD) <= {cond.max():.2e}")
         for f, e in errs.items():
             assert e < TOL, f"iteration {it}: stage {f} rel err {e:.3e} (bar {TOL:.0e})"
         assert bw <= BW_TOL, f"iteration {it}: loading backward error {bw:.3e} (bar {BW_TOL:.0e})"
-    print(f"MISSING_STAGEWISE_WORST {name} flags {flags:#x}: stage {max(worst.values()) / TOL:.3e} x bar,"
+    print(f"MISSING_STAGEWISE_WORST {what}: stage {max(worst.values()) / TOL:.3e} x bar,"
           f" bw {worst_bw / BW_TOL:.3e} x bar")
+    return max(worst.values()), worst_bw
+
+
+@pytest.mark.parametrize("flags", [0, mc.EXACT_RESIDUAL, mc.GUARD_ALL], ids=["default", "exact", "guard_all"])
+@pytest.mark.parametrize("name", ["A", "C"])
+def test_the_sweep_reads_the_completed_data(dcfm, name, flags):
+    _check_sweep(_case(name), _stepped(dcfm, name, "random", flags), f"{name} flags {flags:#x}")
 
 
 def test_yy_is_rewritten_not_incremented(dcfm):
@@ -290,9 +300,8 @@ def _accumulate(dcfm, name, mask, capacity, second_call_at=None):
     return out, s1, s2, sv, cnt, y_start
 
 
-@pytest.mark.parametrize("name", ["A", "C"])
-def test_accumulators(dcfm, name):
-    mask = _mask(name, "edges")
+def _check_accumulators(dcfm, name, mask):
+    """get_imputed's accumulators against host sums of the stepped mu and 1 / ps."""
     has = mask.any(axis=0)
     worst = 0.0
     for capacity, second in ((3, None), (2, None), (3, 5)):
@@ -309,6 +318,12 @@ def test_accumulators(dcfm, name):
         assert e.max() <= ACC_BAR and not got["nvar"][~has].any()
         assert np.array_equal(got["mean"][~mask], got["Y"][~mask]) and np.array_equal(got["m2"][~mask], got["Y"][~mask] ** 2)
     print(f"MISSING_ACC {name}: worst ratio to the 1e-12 bar {worst / ACC_BAR:.3e}")
+    return worst / ACC_BAR
+
+
+@pytest.mark.parametrize("name", ["A", "C"])
+def test_accumulators(dcfm, name):
+    _check_accumulators(dcfm, name, _mask(name, "edges"))
 
 
 def test_capacity_zero_moves_the_chain_and_counts_nothing(dcfm):

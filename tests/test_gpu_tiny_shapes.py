@@ -25,8 +25,9 @@ reference at every case on the CPU).  Every bar is one the project already uses;
                          sit near zero, so no relative bar on the sum: |got - want| <= 1e-10 sum |summands|, the
                          forward bound of a sum.
 
-The per-feature read-outs (probes, precision, loglik, predict, regression, missing, corr, partial corr,
-sigma_apply, sigma_eigs, sigma_solve) at these shapes are not covered here.
+The per-feature read-outs (probes, precision, loglik, predict, regression, missing, corr, partial corr, precision
+mean, second moment, sigma_apply, sigma_eigs, sigma_solve) at these shapes: tests/test_gpu_tiny_readouts.py
+(tests/tiny_readouts.py: their own edges and the cases that reach them).
 
 Measured on the MI355X: DESIGN.md section 2, "Smallest shapes".
 """
